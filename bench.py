@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: training patches/sec of the patch-level hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload swinir_x8|edsr_x8|edsr_x4|edsr_x2]
+    python bench.py --gpus N --steps K --warmup W [--workload swinir_x8|edsr_x8|edsr_x4|edsr_x2] [--full]
+                    [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line; everything else it can measure (the
+eager rates, the live roofline, the forward-only figures, config.secondary, torch_rocm_baseline, cpu_baseline) runs
+behind the timed steps only with --full.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 
 One process per GPU.  With --gpus N > 1 and no WORLD_SIZE in the environment the
 script launches itself under ``python -m torch.distributed.run`` (before any GPU
@@ -17,7 +22,7 @@ optimizer on one synthetic batch of 8 patches per GPU:
 
 Rank 0 prints ONE JSON line.  ``value`` = patches of all ranks / wall time of exactly K steps between
 barrier + synchronize pairs (max over ranks); ``step_ms`` = median / p10 / p90 of the per-step durations
-from HIP events recorded on the compute stream; ``roofline`` = the dominant KERNEL (largest summed launch time) timed
+from HIP events recorded on the compute stream; with --full: ``roofline`` = the dominant KERNEL (largest summed launch time) timed
 live with HIP events around every launch of three eager steps run right BEHIND the timed region (events cannot be recorded
 inside a hipGraph replay and an event pair slows a step: the timed K steps carry none); ``cpu_baseline`` = the oracle (PyTorch-fp32
 CPU restatement, validated against the reference) timed on the host cores on a bounded sample, B=1 and B=8.
@@ -63,7 +68,17 @@ def parse_args(argv=None):
                     help="profiling runs: nothing but the warm-up and the timed training steps (no evaluation figure, no "
                          "secondary workloads, no CPU baseline), so that per-kernel statistics and PMC byte counts divide "
                          "by the step count")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="behind the timed steps, also measure everything beside the headline (eager rates, roofline, "
+                         "forward-only figures, secondary workloads, torch and CPU baselines); the --no-* options and "
+                         "--train-only leave parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (the loss buffer, the updated "
+                         "parameters and their gradients) as DIR/<name>.npy, float32")
+    args = ap.parse_args(argv)
+    if not args.full:           # a plain run: set-up, warm-up, the K timed steps and the result line
+        args.train_only = args.no_roofline = True
+    return args
 
 
 # ------------------------------------------------------------------ parent: self-launch
@@ -103,6 +118,24 @@ def synth_batch(batch, scale, device, seed):
     hr = (torch.rand(batch, 1, 512, 512, generator=g) * 255).round() / 255
     lr = F.interpolate(hr, scale_factor=1.0 / scale, mode="bicubic").clamp(0, 1)
     return lr.to(device), hr.to(device)
+
+
+DUMP_MAX_ELEMS = 6_000_000      # per array: the parameters and gradients of SwinIR x8 stay under 64 MB together
+
+
+def write_outputs(outdir, arrays):
+    """{name: tensor} -> outdir/<name>.npy, flattened to float32.  A tensor of more than DUMP_MAX_ELEMS elements is
+    written as a sample of that many, at sorted indices drawn from a fixed seed (the same ones for the same size), so
+    that two builds of the project compare output for output."""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in arrays.items():
+        v = t.detach().float().reshape(-1).cpu()
+        if v.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMS]
+            v = v[idx.sort().values]
+        np.save(os.path.join(outdir, f"{name}.npy"), v.numpy())
 
 
 def measured_bytes_per_step(workload):
@@ -499,6 +532,14 @@ def worker(args):
     barrier()
     dt = time.perf_counter() - t0
     gpu_legs["timed_steps"] = dt
+    if args.dump_outputs and rank == 0:
+        # what step_fn leaves its caller after the last timed step, before anything below trains on: the loss buffer it
+        # returns, the updated parameters and their gradients (named_parameters order, without the flat buffers' padding)
+        fp = ts.fp
+        write_outputs(args.dump_outputs, {
+            "loss": ts.loss_buf,
+            "params": torch.cat([fp.flat[fp.offsets[k]:fp.offsets[k] + fp.gviews[k].numel()] for k in fp.names]),
+            "grads": torch.cat([fp.gviews[k].reshape(-1) for k in fp.names])})
     # behind the timed region: the same step eagerly (what the earlier rounds' headline timed; ADVICE r5: both methodologies
     # in the line), then three eager steps with HIP events around every launch of the probed op classes (an event pair is two
     # barrier packets: a probed step runs ~18 % slower)

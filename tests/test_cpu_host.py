@@ -675,3 +675,25 @@ def test_bench_self_launch_relays_worker_failure():
         assert p.returncode != 0
         assert '{"metric"' not in p.stdout
         assert "worker launch failed" in p.stderr
+
+
+def test_bench_plain_run_and_output_dump(tmp_path):
+    """A plain `bench.py` run is the headline and nothing else: the eager rates, roofline, forward-only figures, secondary
+    workloads and baselines run only with --full.  --dump-outputs writes float32 .npy files; a vector above the per-array
+    cap becomes a sample at the same seeded indices from run to run, so that two builds compare output for output."""
+    import bench
+    a = bench.parse_args(["--steps", "7"])
+    assert a.steps == 7 and not a.full and a.train_only and a.no_roofline and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", str(tmp_path)])
+    assert a.full and not a.train_only and not a.no_roofline and not a.no_cpu_baseline and a.dump_outputs == str(tmp_path)
+    n = bench.DUMP_MAX_ELEMS + 1000
+    big = torch.arange(n, dtype=torch.float64)
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), {"loss": torch.tensor([0.5, 0.25]), "params": big})
+    loss, params = np.load(tmp_path / "a" / "loss.npy"), np.load(tmp_path / "a" / "params.npy")
+    assert loss.dtype == np.float32 and loss.tolist() == [0.5, 0.25]
+    assert params.dtype == np.float32 and params.shape == (bench.DUMP_MAX_ELEMS,)
+    assert np.all(np.diff(params) > 0) and params[-1] < n                  # distinct sorted elements of the vector
+    assert np.array_equal(params, np.load(tmp_path / "b" / "params.npy"))
+    # what the headline workload dumps (parameters + gradients of SwinIR x8, 7.9 M each) stays under 64 MB
+    assert 2 * bench.DUMP_MAX_ELEMS * 4 < 64e6

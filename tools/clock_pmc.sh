@@ -8,7 +8,7 @@ ROOT=$(pwd)
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE --output-format csv -d "$ROOT/$OUT/run" -- \
-  python3 "$ROOT/bench.py" --workload $WL --steps $STEPS --warmup 2 --no-cpu-baseline --no-roofline > "$ROOT/$OUT/bench.log" 2>&1
+  python3 "$ROOT/bench.py" --workload $WL --steps $STEPS --warmup 2 --full --no-cpu-baseline --no-roofline > "$ROOT/$OUT/bench.log" 2>&1
 cd "$ROOT"
 python3 tools/parse_clock.py "$OUT/run" "$OUT/clock_per_kernel.json"
 rm -rf "$OUT/run"

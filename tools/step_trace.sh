@@ -7,7 +7,7 @@ shift 2
 ROOT=$(pwd)
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d "$ROOT/$OUT/run" -- python3 "$ROOT/bench.py" --workload $WL --train-only --steps 6 --warmup 3 "$@" > "$ROOT/$OUT/bench.json" 2> "$ROOT/$OUT/bench.err" || true
+rocprofv3 --kernel-trace --output-format csv -d "$ROOT/$OUT/run" -- python3 "$ROOT/bench.py" --workload $WL --full --train-only --steps 6 --warmup 3 "$@" > "$ROOT/$OUT/bench.json" 2> "$ROOT/$OUT/bench.err" || true
 cd "$ROOT"
 python3 tools/step_trace.py "$(find "$OUT/run" -name '*kernel_trace.csv' | head -1)" > "$OUT/step.txt"
 rm -rf "$OUT/run"
