@@ -187,7 +187,7 @@ int srhip_resblock64_bwd_f16x2(const float* g, long ldg, const void* W2Th, const
  * activations NHWC fp16 in HBM, the weight = the leading fp16 plane of the srhip_conv3x3_nhwc_f16x2 operand (job kind 4; ps2:
  * mode 12), ONE fp16 MFMA product, f32 accumulate, fp16 out.  Cin a multiple of 32, Cout of 64 (ps2: of 256), pitches multiples
  * of 8 halves.  epi 0 +bias | 1 relu | 2 R + alpha*(acc+bias) | 6 leaky relu(alpha) | 8 relu(R + alpha*(acc+bias)) (R fp16, laid
- * out as Y).  in_bn_coef [4][Cin] (may be NULL): evaluation-mode BatchNorm + ReLU on the input, as srhip_conv3x3_nhwc_split_ex.
+ * out as Y) | 9 R > 0 ? alpha*(acc+bias) : 0 (training, below).  in_bn_coef [4][Cin] (may be NULL): evaluation-mode BatchNorm + ReLU on the input, as srhip_conv3x3_nhwc_split_ex.
  * center_only: the weight is a 1x1 conv held in the centre tap of a 3x3 (the other taps are not multiplied).
  * ps2: the result goes through PixelShuffle(2) into Y [B][2H][2W][Cout/4] (network_nlsn.py:100-118).  Replaces
  * nn.Conv2d + ReLU / ResBlock of network_vdsr.py:24-60, network_drrn.py:22-62, network_nlsn.py:72-128 under torch.autocast-like
@@ -215,6 +215,44 @@ int srhip_conv3x3_ps2_f16x2(const float* X, long ldx, const void* Wh, const floa
 int srhip_conv3x3_ps2_bwd_data_f16x2(const float* dYup, long lddy, const void* Wht, float* dX, long ldx, int B, int H,
                                      int W, int Cout, int Cin, int epi, const float* R, long ldr, float alpha,
                                      void* stream);
+/* ---- fp16-STORAGE TRAINING of EDSR under --amp (conv_h16_bwd.hip, conv_h16.hip): the reference's autocast + GradScaler step
+ * (model_plain.py:318-363, 348, 363): feature maps and activation gradients fp16, one fp16 MFMA product with f32 accumulation,
+ * weight and bias gradients f32.  The body's data gradients are srhip_conv3x3_nhwc_h16 on the data-gradient pack (job kind 4,
+ * data_grad: [9][Cin][Cout]) with epi 2 (R = the skip gradient, alpha 1) or epi 9: R > 0 ? alpha * acc : 0 (the ReLU mask of
+ * the kept fp16 activation times res_scale; network_nlsn.py:72-97).
+ *   srhip_conv3x3_ps2_bwd_data_h16  the upsampler conv's data gradient read through PixelShuffle(2) (network_nlsn.py:100-118):
+ *                                   dYup [B][2H][2W][Cout/4] fp16, Wht the data-gradient pack with mode 16 -> dX [B][H][W][Cin]
+ *                                   fp16 (Cout a multiple of 128); the fp16 twin of srhip_conv3x3_ps2_bwd_data_f16x2
+ *   srhip_conv3x3_wgrad_h16         dW [Cout][Cin][3][3], db [Cout] (may be NULL) of up to 40 problems of one shape from fp16
+ *                                   dY [B][H][W][Cout] and X [B][H][W][Cin] (ps2: dY = the gradient of the PixelShuffle(2)
+ *                                   output [B][2H][2W][Cout/4]); Cout, Cin multiples of 64.  Workspace `part`: n * the floats
+ *                                   srhip_conv3x3_wgrad_h16_plan returns per item, S from the plan.  Deterministic (the runs'
+ *                                   partial sums are added in a fixed order).  Replaces the conv weight gradients autograd runs
+ *                                   under autocast (nn.Conv2d of network_nlsn.py:38-128 on fp16 operands)
+ *   srhip_conv3x3_cin1_wgrad_h16    the 1-channel ends: dw[c][t] = sum_p img[p + d_t] feat[p][c], db[c] = sum_p feat[p][c]
+ *                                   (db may be NULL); img f32 [B][H][W], feat fp16 [B][H][W][C].  The head's weight gradient
+ *                                   (img = the input, feat = its output gradient) and, flip = 1, the tail's (img = dy, feat =
+ *                                   the tail's input); ws: srhip_conv3x3_cin1_wgrad_h16_ws(C) floats
+ *   srhip_conv3x3_cin1_h16_flip     the tail's data gradient: f32 dy [B][H][W] through the mirrored taps of w [1][Co][3][3]
+ *                                   -> fp16 [B][H][W][Co] (srhip_conv3x3_cin1_h16 has no flip)
+ *   srhip_axpby_h16                 y = a y + b x on fp16 tensors (f32 arithmetic), n a multiple of 8: the long skip's
+ *                                   gradient add (network_nlsn.py:363-366)
+ *   srhip_amp_unscale_check         GradScaler.unscale_ with a constant scale (model_plain.py:348-363, tools.py:55): g *=
+ *                                   inv_scale over the flat gradient, and *overflow_flag = 1 if any g before the unscale is
+ *                                   non-finite or |g| >= 65520 (what rounds to inf in fp16: the reference's fp16 conv gradients).
+ *                                   The flag is only ever set (the caller clears it); no host read (capturable). */
+typedef struct { const void* dY; const void* X; float* dW; float* db; } srhip_conv_wgrad_h16_item;
+int srhip_conv3x3_ps2_bwd_data_h16(const void* dYup, long lddy, const void* Wht, void* dX, long ldx, int B, int H, int W,
+                                   int Cout, int Cin, void* stream);
+int srhip_conv3x3_wgrad_h16_plan(int n, int B, int H, int W, int Cout, int Cin, int ps2, int* S, long* part_floats_per_item);
+int srhip_conv3x3_wgrad_h16(const srhip_conv_wgrad_h16_item* items, int n, long lddy, long ldx, int B, int H, int W, int Cout,
+                            int Cin, int ps2, float* part, int S, void* stream);
+long srhip_conv3x3_cin1_wgrad_h16_ws(int C);
+int srhip_conv3x3_cin1_wgrad_h16(const float* img, const void* feat, long ldf, float* dw, float* db, float* ws, int B, int H,
+                                 int W, int C, int flip, void* stream);
+int srhip_conv3x3_cin1_h16_flip(const float* x, const float* w, void* y, long ldy, int B, int H, int W, int Co, void* stream);
+int srhip_axpby_h16(void* y, const void* x, long n, float a, float b, void* stream);
+int srhip_amp_unscale_check(float* g, long n, float inv_scale, int* overflow_flag, void* stream);
 /* The MLP half of a Swin block in one kernel per direction (mlp_f16.hip): the hidden activation goes from the first
  * product's accumulators through registers and LDS into the second product and is never read back from HBM.
  *   forward : h = LN(x) . W1^T + b1 (stats[M][2] = {mean, rstd} of x; W1 gamma-folded, b1 beta-folded),

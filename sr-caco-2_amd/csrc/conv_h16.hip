@@ -91,6 +91,11 @@ __device__ __forceinline__ void h16_epilogue(const ConvH16Args& p, const f32x4 (
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * p.alpha;
     }
+    if (p.epi == 9) {                    // data gradient through a ReLU whose fp16 OUTPUT R was kept, times alpha (res_scale)
+      const h16x8 r = *(const h16x8*)(p.R + pix * p.ldr + col);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = (float)r[e] > 0.f ? v[e] * p.alpha : 0.f;
+    }
     h16x8 o;
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = (_Float16)v[e];
@@ -134,13 +139,23 @@ __global__ void __launch_bounds__(256, 3) k_conv3x3_h16(ConvH16Args p) {
     const int y = y0 + hy - 1, x = x0 + hx - 1;
     inA[it] = y >= 0 && y < p.H && x >= 0 && x < p.Wd && (AN % 256 == 0 || tid + it * 256 < AN);
     const int yc = min(max(y, 0), p.H - 1), xc = min(max(x, 0), p.Wd - 1);
-    offA[it] = (unsigned)((((long)img * p.H + yc) * p.Wd + xc) * p.ldx + c8 * 8) * 2u;
+    offA[it] = p.ps_in ? (unsigned)((((long)img * 2 * p.H + 2 * yc) * (2 * p.Wd) + 2 * xc) * p.ldx + c8 * 8) * 2u
+                       : (unsigned)((((long)img * p.H + yc) * p.Wd + xc) * p.ldx + c8 * 8) * 2u;
   }
+  // ps_in (the data gradient of conv + PixelShuffle(2), read from the gradient of the shuffled image [B][2H][2Wd][K/4]):
+  // input channel sp * (K/4) + cc of pixel (y, x) is channel cc of pixel (2y + (sp >> 1), 2x + (sp & 1)); a 32-channel chunk
+  // lies inside one sub-pixel plane (K/4 a multiple of 32), so a chunk is one byte offset from the pixel's (2y, 2x) base
+  const int fs = p.K >> 2;
+  auto chunk_off = [&](int kc) -> long {
+    if (!p.ps_in) return (long)kc * 64;
+    const int sp = (kc * 32) / fs, cc = kc * 32 - sp * fs;
+    return (((long)(sp >> 1) * 2 * p.Wd + (sp & 1)) * p.ldx + cc) * 2;
+  };
   // input prologue (MemNet's BN-ReLU-conv, network_memnet.py:27-34): relu((x - mean) k + beta) on the thread's eight
   // channels of the chunk (256 % 4 == 0: the same group in every iteration), before the padding zeros go in
   f32x4 bm[2], bk[2], bb[2];
   auto load_a = [&](int kc, u32x4 (&ra)[AIT]) {
-    const char* base = (const char*)p.X + (long)kc * 64;
+    const char* base = (const char*)p.X + chunk_off(kc);
 #pragma unroll
     for (int it = 0; it < AIT; ++it) ra[it] = inA[it] ? *(const u32x4*)(base + offA[it]) : u32x4{0u, 0u, 0u, 0u};
   };
@@ -655,9 +670,10 @@ __global__ void __launch_bounds__(256, 3) k_srcnn_h16(SrcnnH16Args p) {
 // 1 -> Co conv (f32 image in, fp16 features out), act 0 none | 1 ReLU | 2 LeakyReLU(alpha).  A thread owns 8 output channels of one pixel.
 __global__ void __launch_bounds__(256) k_cin1_h16(const float* __restrict__ x, const float* __restrict__ w,
                                                   const float* __restrict__ bias, _Float16* __restrict__ y, long ldy, int B,
-                                                  int H, int W, int Co, int act, float alpha) {
+                                                  int H, int W, int Co, int act, float alpha, int flip) {
   extern __shared__ float wl[];                  // [9][Co] + [Co]
-  for (int i = threadIdx.x; i < 9 * Co; i += 256) wl[(i % 9) * Co + i / 9] = w[i];
+  // flip: w is [1][Co][3][3] (the same bytes as [Co][1][3][3]) read with the taps mirrored -- the data gradient of a Co -> 1 conv
+  for (int i = threadIdx.x; i < 9 * Co; i += 256) wl[(flip ? 8 - i % 9 : i % 9) * Co + i / 9] = w[i];
   for (int i = threadIdx.x; i < Co; i += 256) wl[9 * Co + i] = bias ? bias[i] : 0.f;
   __syncthreads();
   const int G = Co >> 3;
@@ -749,8 +765,12 @@ int sr_conv3x3_h16(ConvH16Args& p, hipStream_t st) {
   SR_REQUIRE(p.K % 32 == 0 && p.K >= 32 && p.K <= 4096 && p.N % 64 == 0 && p.N <= 4096,
              "conv3x3_h16: Cin = %d (a multiple of 32), Cout = %d (a multiple of 64), both <= 4096", p.K, p.N);
   SR_REQUIRE(p.ldx % 8 == 0 && p.ldy % 8 == 0 && (!p.R || p.ldr % 8 == 0), "conv3x3_h16: pixel pitches must be multiples of 8 halves");
-  SR_REQUIRE(p.epi == 0 || p.epi == 1 || p.epi == 6 || ((p.epi == 2 || p.epi == 8) && p.R),
-             "conv3x3_h16: epilogue %d (0, 1, 6, 2 / 8 with R)", p.epi);
+  SR_REQUIRE(p.epi == 0 || p.epi == 1 || p.epi == 6 || ((p.epi == 2 || p.epi == 8 || p.epi == 9) && p.R),
+             "conv3x3_h16: epilogue %d (0, 1, 6, 2 / 8 / 9 with R)", p.epi);
+  SR_REQUIRE(!p.ps_in || (p.K % 128 == 0 && !p.ps && !p.center_only && !p.in_bn),
+             "conv3x3_h16, input through PixelShuffle(2): Cin %% 128 == 0 (Cin=%d), no output shuffle, 3x3, no prologue", p.K);
+  SR_REQUIRE(!p.ps_in || (long)p.B * 4 * p.H * p.Wd * p.ldx < (1L << 31),
+             "conv3x3_h16: shuffled input larger than 4 GiB (32-bit staging offsets)");
   SR_REQUIRE(!p.ps || (p.N % 256 == 0 && !p.R), "conv3x3_h16 + PixelShuffle(2): Cout %% 256 == 0 and no residual (Cout=%d)", p.N);
   SR_REQUIRE(p.B > 0 && p.H > 0 && p.Wd > 0, "conv3x3_h16: empty image");
   SR_REQUIRE((long)p.B * p.H * p.Wd * p.ldx < (1L << 31), "conv3x3_h16: input larger than 4 GiB (32-bit staging offsets)");
@@ -772,7 +792,7 @@ int sr_conv3x3_h16(ConvH16Args& p, hipStream_t st) {
     // A fragments from LDS and issue 1.1 us of MFMAs -- three throughput limits of the same size that overlap only partly.
     static const int pers = [] { const char* e = sr_getenv("SRHIP_H16_PERSISTENT"); return e ? atoi(e) : 0; }();
     const long ntiles = (long)grid.x;
-    if (pers && ntiles >= 4 * 768 && ntiles < (1L << 30)) {
+    if (pers && !p.ps_in && ntiles >= 4 * 768 && ntiles < (1L << 30)) {
       if (p.in_bn) hipLaunchKernelGGL(k_conv3x3_h16p<true>, dim3(768), dim3(256), h16_lds(4), st, p, (int)ntiles);
       else hipLaunchKernelGGL(k_conv3x3_h16p<false>, dim3(768), dim3(256), h16_lds(4), st, p, (int)ntiles);
     }
@@ -783,13 +803,13 @@ int sr_conv3x3_h16(ConvH16Args& p, hipStream_t st) {
 }
 
 int sr_conv_cin1_h16(const float* x, const float* w, const float* bias, void* y, long ldy, int B, int H, int W, int Co, int act,
-                     float alpha, hipStream_t st) {
+                     float alpha, hipStream_t st, int flip) {
   SR_REQUIRE(x && w && y, "conv_cin1_h16: null operand");
   SR_REQUIRE(Co % 8 == 0 && Co <= 1024 && ldy % 8 == 0, "conv_cin1_h16: Cout = %d (a multiple of 8, <= 1024)", Co);
   const long n = (long)B * H * W * (Co / 8);
   if (n <= 0) return 0;
   const int grid = (int)(n / 256 + 1 < 8192 ? n / 256 + 1 : 8192);
-  hipLaunchKernelGGL(k_cin1_h16, dim3(grid), dim3(256), (size_t)10 * Co * 4, st, x, w, bias, (_Float16*)y, ldy, B, H, W, Co, act, alpha);
+  hipLaunchKernelGGL(k_cin1_h16, dim3(grid), dim3(256), (size_t)10 * Co * 4, st, x, w, bias, (_Float16*)y, ldy, B, H, W, Co, act, alpha, flip);
   SR_LAUNCH_CHECK("k_cin1_h16");
   return 0;
 }

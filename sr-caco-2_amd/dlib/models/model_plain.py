@@ -49,7 +49,8 @@ class ModelPlain:
         self.device = torch.device(f'cuda:{dev_id}')
         self.netG = define_G(args).to(self.device)
         # --amp: the reference trains and evaluates under autocast (model_plain.py:322-327); here evaluation takes the
-        # reduced-precision kernels and a TRAINING step under --amp raises (optimize_parameters): it is not implemented, and
+        # reduced-precision kernels, EDSR trains on fp16 storage (TrainStep(amp=True)), and a TRAINING step of any other net
+        # under --amp raises (optimize_parameters): it is not implemented, and
         # training f32-grade under a flag that asks for something else would be a silent change of the run
         self.netG.amp = bool(getattr(args, 'amp', False))
         for k in ('G_regularizer_orthstep', 'G_regularizer_clipstep'):
@@ -87,7 +88,8 @@ class ModelPlain:
             import torch.distributed as dist
             world, pg = dist.get_world_size(), dist.group.WORLD
         self.step_fn = TrainStep(self.netG, self.loss_fn.terms(), process_group=pg, world_size=world,
-                                 clipgrad=float(self._opt('G_optimizer_clipgrad', 0.0) or 0.0), ema_decay=self.E_decay)
+                                 clipgrad=float(self._opt('G_optimizer_clipgrad', 0.0) or 0.0), ema_decay=self.E_decay,
+                                 amp=self._amp_train_ok())
         self.step_fn.opt = Optimizer(self.step_fn.fp, **optimizer_config(self.args))
         self.G_optimizer = self.step_fn.opt
         self.load_optimizers()
@@ -199,11 +201,27 @@ class ModelPlain:
             rank = f' [rank {dist.get_rank()}]'
         print(f"[libsrhip]{rank} training-step capture failed ({why}): eager steps from here on", flush=True)
 
+    # the nets whose engine trains under --amp (fp16 storage + the GradScaler's rules: TrainStep(amp=True))
+    AMP_TRAIN_NETS = ("EDSR_LIIF",)
+
+    def _amp_train_ok(self):
+        """--amp and an engine with an fp16-storage training path whose configuration it supports (EDSREngine.amp_train_ok);
+        an EDSR the engine cannot take raises here with the reason."""
+        if not getattr(self.netG, 'amp', False):
+            return False
+        eng = getattr(self.netG, 'engine', None)
+        if eng is None or not hasattr(eng, 'amp_train_ok'):
+            return False
+        if not eng.amp_train_ok():
+            raise NotImplementedError(eng._amp_train_refusal())
+        return True
+
     def optimize_parameters(self, epoch: int, current_step: int):
-        if getattr(self.netG, 'amp', False):
-            raise NotImplementedError("--amp True in training (torch.cuda.amp autocast + GradScaler, model_plain.py:322-327,"
-                                      "348,363) is not implemented on this path: the step is f32-grade only; --amp selects the "
-                                      "reduced-precision kernels for evaluation (model.test / eval.py)")
+        if getattr(self.netG, 'amp', False) and not getattr(self.step_fn, 'amp', False):
+            raise NotImplementedError(f"--amp True in training (torch.cuda.amp autocast + GradScaler, model_plain.py:322-327,"
+                                      f"348,363) is implemented for {', '.join(self.AMP_TRAIN_NETS)} only; this net "
+                                      f"({type(self.netG).__name__}) trains f32-grade, and --amp selects its reduced-precision "
+                                      f"kernels for evaluation (model.test / eval.py)")
         self._weights_version += 1
         done = False
         if self._train_graph_on():

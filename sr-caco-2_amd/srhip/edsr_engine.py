@@ -40,6 +40,7 @@ class EDSREngine:
         self.side_wgrad = os.environ.get("SRHIP_EDSR_SIDE_WGRAD", "0") == "1"
         self.wstream = None
         self.saved = None
+        self.saved_h16 = None           # what forward_h16(save=True) kept for backward_h16
         # Upsampler stage = conv F -> 4F + PixelShuffle(2) as one kernel per direction (no [B,H,W,4F] tensor,
         # no shuffle launches); SRHIP_FUSE_PS=0: conv + index kernel
         self.fuse_ps = self.ws.use_bx3 and ops.ps2_fusable(self.F, 4 * self.F) and \
@@ -96,28 +97,57 @@ class EDSREngine:
         return (self.ws.use_bx3 and self.fuse_ps and self.F % 64 == 0
                 and all(self.ws[n + ".wp"].fmt == 1 for n, _ in self._body_convs()))
 
-    def forward_h16(self, x):
-        """--amp evaluation on fp16 storage (conv_h16.hip): the same launches with float16 feature maps, one fp16 product;
-        the upsampler's conv stores through its PixelShuffle(2)."""
+    def amp_train_ok(self):
+        """Whether this configuration trains under --amp on fp16 storage (forward_h16(save=True) + backward_h16): the fp16x2
+        packs of every conv in both directions, 64 .. 256 features, a power of two (the 1-channel ends' weight gradient)."""
+        if not self.prepared:
+            self.prepare()
+        return (self._h16_ok() and self.F in (64, 128, 256)
+                and all(self.ws[n + ".wpt"].fmt == 1 for n, _ in self._body_convs()))
+
+    def _amp_train_refusal(self):
+        return (f"EDSR under --amp training runs on fp16 storage only with the fp16x2 conv packs of every conv, the fused "
+                f"PixelShuffle upsampler and n_feats in (64, 128, 256); this net: n_feats {self.F}, fp16x2 packs "
+                f"{self.ws.use_bx3}, fused PixelShuffle {self.fuse_ps} (SRHIP_MM / SRHIP_F16X2_CONV* / SRHIP_FUSE_PS switch "
+                f"them off)")
+
+    def forward_h16(self, x, save=False):
+        """fp16 storage (conv_h16.hip): the same launches with float16 feature maps, one fp16 product; the upsampler's conv
+        stores through its PixelShuffle(2).  save=False: --amp evaluation ("h." buffers, two rotating block outputs).
+        save=True: the --amp training forward (autocast's fp16 maps, model_plain.py:322-327): every map the backward reads
+        is kept in "a." buffers of its own -- an evaluation forward in between overwrites none of them."""
         net, F = self.net, self.F
         B, H, W = x.shape
         dev = x.device
+        if save and not self.amp_train_ok():
+            raise NotImplementedError(self._amp_train_refusal())
+        tag = "a." if save else "h."
 
         def buf(name, *shape):
-            return self.bufs.get("h." + name, *shape, device=dev, dtype=torch.float16)
+            return self.bufs.get(tag + name, *shape, device=dev, dtype=torch.float16)
         f0 = ops.conv3x3_cin1_h16(x, net.head[0].weight.data, net.head[0].bias.data, F, out=buf("f0", B, H, W, F))
         r, rs = f0, float(net.res_scale)
+        blocks = []
         for k in range(self.nb):
-            a = ops.conv3x3_h16(r, self.ws[f"b{k}.0.wp"], net.body[k].body[0].bias.data, F, out=buf("a", B, H, W, F), epi=1)
-            r = ops.conv3x3_h16(a, self.ws[f"b{k}.2.wp"], net.body[k].body[2].bias.data, F, out=buf(f"r{k % 2}", B, H, W, F),
-                                epi=2, R=r, alpha=rs)
+            a = ops.conv3x3_h16(r, self.ws[f"b{k}.0.wp"], net.body[k].body[0].bias.data, F,
+                                out=buf(f"a{k}" if save else "a", B, H, W, F), epi=1)
+            rn = ops.conv3x3_h16(a, self.ws[f"b{k}.2.wp"], net.body[k].body[2].bias.data, F,
+                                 out=buf(f"r{k if save else k % 2}", B, H, W, F), epi=2, R=r, alpha=rs)
+            blocks.append((r, a))
+            r = rn
         u = ops.conv3x3_h16(r, self.ws["bend.wp"], net.body[self.nb].bias.data, F, out=buf("rb", B, H, W, F), epi=2, R=f0)
         h, w = H, W
+        ups = []
         for i in range(self.stages):
+            ups.append(u)
             u = ops.conv3x3_h16(u, self.ws[f"up{i}.wp"], net.tail[0][2 * i].bias.data, 4 * F, out=buf(f"u{i}", B, 2 * h, 2 * w, F),
                                 ps2=True)
             h, w = 2 * h, 2 * w
-        y = ops.conv3x3_cout1_h16(u, net.tail[1].weight.data, net.tail[1].bias.data)
+        # (training: the f32 output in the f32 step's own buffer, which ModelPlain.E reads)
+        y = ops.conv3x3_cout1_h16(u, net.tail[1].weight.data, net.tail[1].bias.data,
+                                  out=self.bufs.get("t.y", B, h, w, device=dev) if save else None)
+        if save:
+            self.saved_h16 = dict(x=x, blocks=blocks, r_last=r, ups=ups, u_last=u, B=B, H=H, W=W)
         return y.view(B, 1, h, w)
 
     def forward(self, x, dp=None, save=True):
@@ -308,4 +338,59 @@ class EDSREngine:
         if need_dx:
             wflip = net.head[0].weight.data.flip(2, 3).reshape(1, F, 3, 3).contiguous()
             return ops.conv3x3_cout1_fwd(g, wflip, None)
+        return None
+
+    def backward_h16(self, dy, grads, need_dx=False, on_layer_done=None, grads_zeroed=False):
+        """backward() on fp16 storage, launch for launch (the reference's backward under autocast: fp16 activation gradients,
+        fp16 products, f32 accumulation; model_plain.py:348): dy f32 (the loss gradient, already times the loss scale) ->
+        grads (f32).  The data gradients are conv3x3_h16 on the data-gradient packs (epi 9: the ReLU mask of the kept fp16
+        activation times res_scale; epi 2: + the skip gradient), the upsampler's read through its PixelShuffle(2); every
+        weight gradient of the body is one batched fp16 contraction behind the chain."""
+        sv = self.saved_h16
+        assert sv is not None, "backward_h16() without a saved forward_h16(save=True)"
+        if need_dx:
+            raise NotImplementedError("backward_h16: the input gradient (EDSR is a first layer; nothing asks for it)")
+        net, F = self.net, self.F
+        B, H, W = sv["B"], sv["H"], sv["W"]
+        dev = dy.device
+        rs = float(net.res_scale)
+
+        def buf(name, *shape):
+            return self.bufs.get("ag." + name, *shape, device=dev, dtype=torch.float16)
+
+        def G(name):
+            return grads[name]
+
+        s = net.scale
+        dy = dy.reshape(B, H * s, W * s).contiguous()
+        # tail conv F -> 1: the weight gradient = the 1-channel form with dy as the image and mirrored taps; data gradient
+        # = dy through the mirrored taps into fp16
+        ops.conv3x3_cin1_wgrad_h16(dy, sv["u_last"], G("tail.1.weight"), None, flip=True)
+        ops.sum_into(dy, G("tail.1.bias"))
+        h, w = H * s, W * s
+        du = ops.conv3x3_cin1_h16_flip(dy, net.tail[1].weight.data, F, out=buf(f"du{self.stages}", B, h, w, F))
+        for i in reversed(range(self.stages)):
+            h, w = h // 2, w // 2
+            ops.conv3x3_wgrad_h16([(du, sv["ups"][i], G(f"tail.0.{2 * i}.weight"), G(f"tail.0.{2 * i}.bias"))], ps2=True)
+            du = ops.conv3x3_ps2_bwd_data_h16(du, self.ws[f"up{i}.wpt"], buf(f"du{i}", B, h, w, F))
+        drb = du                                             # grad wrt rb (= also grad wrt f0 via the skip)
+        wg = [(drb, sv["r_last"], G(f"body.{self.nb}.weight"), G(f"body.{self.nb}.bias"))]
+        gs = [buf(f"g{k}", B, H, W, F) for k in range(self.nb + 1)]      # gs[k]: gradient wrt block k's input
+        g = gs[self.nb]
+        ops.conv3x3_h16(drb, self.ws["bend.wpt"], None, F, out=g)
+        for k in reversed(range(self.nb)):
+            r_in, a = sv["blocks"][k]
+            p = f"body.{k}.body."
+            # r_out = rs*(conv2(a)+b2) + r_in ;  a = relu(conv1(r_in)+b1)
+            wg.append((g, a, G(p + "2.weight"), G(p + "2.bias")))
+            da = ops.conv3x3_h16(g, self.ws[f"b{k}.2.wpt"], None, F, out=buf(f"da{k}", B, H, W, F), epi=9, R=a, alpha=rs)
+            wg.append((da, r_in, G(p + "0.weight"), G(p + "0.bias")))
+            g = ops.conv3x3_h16(da, self.ws[f"b{k}.0.wpt"], None, F, out=gs[k], epi=2, R=g)     # + skip gradient
+        ops.conv3x3_wgrad_h16(wg)
+        ops.axpby_h16(g, drb, 1.0, 1.0)                      # long skip: rb = conv(body) + f0
+        ops.conv3x3_cin1_wgrad_h16(sv["x"], g, G("head.0.weight"), G("head.0.bias"))
+        if rs != 1.0:                # d(conv2 weights) = rs * (g (x) a): g was used unscaled above
+            for k in range(self.nb):
+                for nm in (f"body.{k}.body.2.weight", f"body.{k}.body.2.bias"):
+                    ops.axpby(G(nm), G(nm), 0.0, rs)
         return None

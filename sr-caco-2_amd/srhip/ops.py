@@ -934,6 +934,96 @@ def conv3x3_cout1_h16(x, w, bias, add=None, out=None, in_bn=None):
     return out
 
 
+def conv3x3_ps2_bwd_data_h16(dYup, Wpt, out):
+    """fp16 data gradient of the conv under a PixelShuffle(2) read from the gradient of the shuffled image (srhip_conv3x3_ps2_bwd
+    _data_h16): dYup float16 [B,2H,2W,F], Wpt the fp16x2 data-gradient pack (PrepTable.conv(data_grad=True, ps2=True)) -> out
+    float16 [B,H,W,Cin]."""
+    assert isinstance(Wpt, Bx3) and Wpt.fmt == 1, "conv3x3_ps2_bwd_data_h16: fp16x2 weight planes"
+    B, H, W, Cin = out.shape
+    F = dYup.shape[3]
+    assert Wpt.rows == 9 * Cin and Wpt.K == 4 * F and tuple(dYup.shape) == (B, 2 * H, 2 * W, F)
+    assert dYup.is_contiguous() and out.is_contiguous()
+    call("srhip_conv3x3_ps2_bwd_data_h16", _ph(dYup), dYup.stride(2), _p(Wpt.planes), _ph(out), out.stride(2), B, H, W, 4 * F,
+         Cin, _st())
+    return out
+
+
+class _ConvWgradH16Item(ctypes.Structure):   # srhip_conv_wgrad_h16_item (include/srhip.h)
+    _fields_ = [("dY", ctypes.c_void_p), ("X", ctypes.c_void_p), ("dW", ctypes.c_void_p), ("db", ctypes.c_void_p)]
+
+
+def conv3x3_wgrad_h16(items, ps2=False):
+    """items: sequence of (dY float16 NHWC [B,H,W,Cout] (ps2: [B,2H,2W,Cout/4], the gradient of the PixelShuffle(2) output),
+    X float16 NHWC [B,H,W,Cin], dW [Cout,Cin,3,3] f32, db [Cout] f32 or None) of ONE shape -> the weight / bias gradients by one
+    fp16 contraction + one reducer launch per 40 items (srhip_conv3x3_wgrad_h16)."""
+    dY0, X0 = items[0][0], items[0][1]
+    B, H, W, Cin = X0.shape
+    Cout = items[0][2].shape[0]
+    assert tuple(dY0.shape) == ((B, 2 * H, 2 * W, Cout // 4) if ps2 else (B, H, W, Cout))
+    for j0 in range(0, len(items), 40):
+        chunk = items[j0:j0 + 40]
+        n = len(chunk)
+        S = ctypes.c_int(0)
+        per = ctypes.c_long(0)
+        call("srhip_conv3x3_wgrad_h16_plan", n, B, H, W, Cout, Cin, int(bool(ps2)), ctypes.addressof(S), ctypes.addressof(per))
+        part = SCRATCH.get("wgh16_part", n * per.value, device=dY0.device)
+        arr = (_ConvWgradH16Item * n)()
+        for k, (dY, X, dW, db) in enumerate(chunk):
+            _chk(dW, db)
+            assert dY.shape == dY0.shape and X.shape == X0.shape and dY.is_contiguous() and X.is_contiguous()
+            assert dW.is_contiguous() and tuple(dW.shape) == (Cout, Cin, 3, 3)
+            arr[k].dY, arr[k].X, arr[k].dW, arr[k].db = _ph(dY), _ph(X), _p(dW), _p(db)
+
+        def run():
+            call("srhip_conv3x3_wgrad_h16", ctypes.addressof(arr), n, dY0.stride(2), X0.stride(2), B, H, W, Cout, Cin,
+                 int(bool(ps2)), _p(part), S.value, _st())
+        if probe.on("conv_tn_h16"):
+            T = B * H * W
+            with probe.timed(("conv_tn_h16", f"x{n}", T, Cout, Cin), 18.0 * T * Cout * Cin * n,
+                             2.0 * n * (T * Cin + T * Cout) + 4.0 * n * S.value * Cout * (9 * Cin + 1) * 2):
+                run()
+        else:
+            run()
+
+
+def conv3x3_cin1_wgrad_h16(img, feat, dw, db, flip=False):
+    """The 1-channel ends on fp16 features (srhip_conv3x3_cin1_wgrad_h16): img f32 [B,H,W], feat float16 [B,H,W,C] ->
+    dw[c][t] = sum_p img[p + d_t] feat[p][c] (flip: taps mirrored), db[c] = sum_p feat[p][c] (db may be None)."""
+    _chk(img, dw, db)
+    B, H, W = img.shape
+    C = feat.shape[3]
+    assert img.is_contiguous() and feat.stride(3) == 1 and dw.is_contiguous() and dw.numel() == 9 * C
+    ws = SCRATCH.get("cin1h_ws", lib.srhip_conv3x3_cin1_wgrad_h16_ws(C), device=img.device)
+    call("srhip_conv3x3_cin1_wgrad_h16", _p(img), _ph(feat), feat.stride(2), _p(dw), _p(db), _p(ws), B, H, W, C, int(bool(flip)),
+         _st())
+
+
+def conv3x3_cin1_h16_flip(dy, w, Co, out=None):
+    """The tail's data gradient (srhip_conv3x3_cin1_h16_flip): f32 dy [B,H,W] through the mirrored taps of w [1,Co,3,3] ->
+    float16 [B,H,W,Co]."""
+    _chk(dy, w)
+    B, H, W = dy.shape
+    assert dy.is_contiguous() and w.is_contiguous() and w.numel() == 9 * Co
+    if out is None:
+        out = torch.empty(B, H, W, Co, device=dy.device, dtype=torch.float16)
+    call("srhip_conv3x3_cin1_h16_flip", _p(dy), _p(w), _ph(out), out.stride(2), B, H, W, Co, _st())
+    return out
+
+
+def axpby_h16(y, x, a, b):
+    """y = a y + b x on float16 tensors of one size (f32 arithmetic)."""
+    assert y.is_contiguous() and x.is_contiguous() and y.numel() == x.numel()
+    call("srhip_axpby_h16", _ph(y), _ph(x), y.numel(), float(a), float(b), _st())
+
+
+def amp_unscale_check(g, inv_scale, overflow_flag):
+    """g *= inv_scale; overflow_flag[0] = 1 if any g was non-finite or >= 65520 in magnitude before (srhip_amp_unscale_check:
+    the GradScaler's unscale_ + found_inf with a constant scale).  The flag is only ever set."""
+    _chk(g, overflow_flag)
+    assert g.dtype == torch.float32 and overflow_flag.dtype == torch.int32 and g.is_contiguous()
+    call("srhip_amp_unscale_check", _p(g), g.numel(), float(inv_scale), _p(overflow_flag), _st())
+
+
 def srcnn_fwd_h16(patches, W1p, b1, W2p, b2, w3, b3, out, image=None):
     """SRCNN's three layers in one launch (srhip_srcnn_fwd_h16): patches [T, 32] float16 (or None with image [B, H, W] f32: the
     patch matrix is built inside), W1p / W2p = centre-tap fp16x2 conv operands of [1024, 32] / [128, 1024], w3 [128], b3 [1]

@@ -386,12 +386,19 @@ class TrainStep:
     'norm_laplace'|'norm_lv', lam, norm, ksz)  (MasterLoss = their sum,
     dlib/loss/master.py:46-56)."""
 
+    AMP_SCALE = 65536.0     # GradScaler(enabled=args.amp) is made inside optimize_parameters: every step starts from its
+                            # init_scale 2^16 and the update() at the end is thrown away (model_plain.py:318-363)
+
     def __init__(self, net, loss_terms=(("l1", 1.0),), optimizer=None, process_group=None,
-                 world_size=1, clipgrad=0.0, ema_decay=0.0):
+                 world_size=1, clipgrad=0.0, ema_decay=0.0, amp=False):
         """clipgrad > 0: torch.nn.utils.clip_grad_norm_(max_norm=clipgrad, norm_type=2) of the (averaged) gradient in front of
         the optimizer (G_optimizer_clipgrad, model_plain.py:350-361).  ema_decay > 0: an exponential moving average of the
         weights is kept in `self.ema_flat` (layout of fp.flat) and updated behind every applied step (E_decay, netE:
-        model_plain.py:46-47,393-394, model_base.py:213-219)."""
+        model_plain.py:46-47,393-394, model_base.py:213-219).  amp: the reference's --amp step (autocast + a fresh
+        GradScaler per step, model_plain.py:318-363) on the engine's fp16-storage path (forward_h16(save=True) /
+        backward_h16): dy times 2^16 behind the loss, the gradient unscaled and checked for fp16 overflow behind the
+        backward, the update skipped on overflow -- the EMA and the LR schedule still advance, as update_E and
+        update_learning_rate do in the reference."""
         self.net = net
         self.fp = FlatParams(net)
         net.weights_changed()
@@ -410,6 +417,17 @@ class TrainStep:
         # caller last looked (ModelPlain.check_finite)
         self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
         self.sticky = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.amp = bool(amp)
+        if self.amp:
+            eng = net.engine
+            if not hasattr(eng, "backward_h16"):
+                raise NotImplementedError(f"--amp training: {type(net).__name__} has no fp16-storage training path")
+            if not eng.amp_train_ok():
+                raise NotImplementedError(eng._amp_train_refusal())
+            # overflow: THIS step's GradScaler found_inf (kept apart from the non-finite-loss flag: an overflow skips
+            # optimizer.step() only -- the EMA still moves and nothing is sticky); skip = flag OR overflow
+            self.overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.skip = torch.zeros(1, dtype=torch.int32, device=dev)
         self.comm_stream = torch.cuda.Stream(device=dev) if self.ddp else None
         self.buckets = self._make_buckets() if self.ddp else []
         # SRHIP_COMM=cabi: the gradient exchange through the C-ABI's own RCCL communicator (srhip_allreduce_*: what a caller
@@ -604,10 +622,12 @@ class TrainStep:
         assert (h, w) == tuple(xi.shape[1:3]), \
             "training patches must not need padding (SwinIR: multiples of the 8x8 window)"
         self.flag.zero_()
+        if self.amp:
+            self.overflow.zero_()
         self.sync_buffers()
         if dp is None:
             dp = net.sample_drop_path(xi.shape[0], xi.device)
-        y = net.engine.forward(xi, dp, save=True)
+        y = net.engine.forward_h16(xi, save=True) if self.amp else net.engine.forward(xi, dp, save=True)
         mean = getattr(net, "mean", None)
         if torch.is_tensor(mean) and bool((mean != 0).any()):
             # y / img_range + mean (network_swinir.py:968; RGB only): the mean as an image, one launch with the scale
@@ -632,15 +652,25 @@ class TrainStep:
             hook = self.reducer.bucket_done
         if self.inv_range != 1.0:
             ops.axpby(dy, dy, self.inv_range, 0.0)
+        if self.amp:                         # scaler.scale(loss).backward(): the logged loss values stay unscaled
+            ops.axpby(dy, dy, self.AMP_SCALE, 0.0)
         # every gradient kernel OVERWRITES its tensor (the LayerNorm-affine sums are two-stage and deterministic too);
         # the memset only keeps a parameter without a gradient path (and the alignment padding) at zero
         self.fp.grad.zero_()
         if d_inter is not None:
             net.engine.backward(dy, self.fp.gviews, on_layer_done=hook, grads_zeroed=True, d_inter=d_inter)
+        elif self.amp:
+            net.engine.backward_h16(dy, self.fp.gviews, on_layer_done=hook, grads_zeroed=True)
         else:
             net.engine.backward(dy, self.fp.gviews, on_layer_done=hook, grads_zeroed=True)
         # one device flag: non-finite loss -> the optimizer kernel skips the update
         ops.nonfinite_flag(self.loss_buf, self.flag)
+        if self.amp:
+            # scaler.unscale_ / found_inf on this rank's gradient, in front of the exchange (the reference's per-rank fp16
+            # gradients are what overflow); the flag is MAX-reduced, so every rank skips the same update
+            ops.amp_unscale_check(self.fp.grad, 1.0 / self.AMP_SCALE, self.overflow)
+            if self.ddp:
+                self.reducer.reduce_flag(self.overflow)
         if self.ddp:
             self.reducer.finish(self.flag)
         for t in self.loss_terms:            # parameter-space term: lam*sign(w) joins the (summed) gradients;
@@ -649,8 +679,12 @@ class TrainStep:
         torch.maximum(self.sticky, self.flag, out=self.sticky)
         if self.clipgrad > 0:                # on the averaged gradient, as the reference clips behind DDP's all-reduce
             ops.grad_norm_clip(self.fp.grad, 1.0 / self.world, self.clipgrad, self.clip_state)
-        self.opt.step(gscale=1.0 / self.world, skip_flag=self.flag, host_side=host_side)
-        if self.ema_flat is not None:
+        skip = self.flag
+        if self.amp:                         # scaler.step skips optimizer.step() on found_inf
+            torch.maximum(self.flag, self.overflow, out=self.skip)
+            skip = self.skip
+        self.opt.step(gscale=1.0 / self.world, skip_flag=skip, host_side=host_side)
+        if self.ema_flat is not None:        # (update_E runs behind a skipped scaler.step too: the loss flag only)
             ops.ema_update(self.ema_flat, self.fp.flat, self.ema_decay, self.flag)
         return self.loss_buf
 
