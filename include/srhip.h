@@ -253,6 +253,37 @@ int srhip_conv3x3_cin1_wgrad_h16(const float* img, const void* feat, long ldf, f
 int srhip_conv3x3_cin1_h16_flip(const float* x, const float* w, void* y, long ldy, int B, int H, int W, int Co, void* stream);
 int srhip_axpby_h16(void* y, const void* x, long n, float a, float b, void* stream);
 int srhip_amp_unscale_check(float* g, long n, float inv_scale, int* overflow_flag, void* stream);
+/* ---- fp16-STORAGE TRAINING of DRRN under --amp (conv_h16_bwd.hip, conv_h16.hip): network_drrn.py:22-126 run under
+ * autocast (model_plain.py:322-348).  One residual unit (ReLU, conv_a, ReLU, conv_b, + x0) is applied U times with SHARED
+ * weights, so each weight gradient is a sum over U applications and the identity gradient into x0 a sum over U units.
+ *   srhip_conv3x3_wgrad_shared_h16  srhip_conv3x3_wgrad_h16 for weights shared by several applications: the same fp16
+ *                                   contraction, one launch per application (no ps2); accumulate = 0: dW = this
+ *                                   application's sum, 1: dW += it (db likewise, may be NULL).  Calling it once per
+ *                                   application in a fixed order makes the sum bit-identical from run to run.  The items of
+ *                                   ONE launch must have disjoint outputs, and no output may overlap any operand or the
+ *                                   workspace (byte ranges are compared).  Workspace: n * the floats
+ *                                   srhip_conv3x3_wgrad_shared_h16_plan returns per item, S from that plan.  Replaces the
+ *                                   weight gradient autograd accumulates over the U applications of the autocast fp16 copy of
+ *                                   trunk.residual_unit.{1,3}.weight (network_drrn.py:64-104)
+ *   srhip_conv3x3_dgrad_relu_acc_h16 the unit's data gradient through a conv and the ReLU in front of it: dY fp16
+ *                                   [B][H][W][Cout] through the data-gradient pack Wht (job kind 4, data_grad) -> dX fp16
+ *                                   [B][H][W][Cin], masked by R > 0 (R = the kept fp16 ReLU output).  mode 0: dX = mask *
+ *                                   acc, then the f32 accumulator G [B][H][W][Cin] += dX (the identity gradient each unit
+ *                                   sends to x0); mode 1: dX = mask * (acc + G) (the first unit, whose input IS x0).  dX may
+ *                                   not overlap dY, R or G, nor G overlap dY or R (ranges).  ldg a multiple of 8, G 16-byte
+ *                                   aligned.  Replaces the conv / ReLU / residual-add backward of network_drrn.py:64-104
+ *   srhip_conv3x3_cin1_h16_flip_mask the tail's data gradient through the ReLU in front of it: f32 dy [B][H][W] through the
+ *                                   mirrored taps of w [1][Co][3][3] -> fp16 y [B][H][W][Co], zero where R <= 0 (R = the
+ *                                   kept fp16 ReLU input of the tail); G (may be NULL): f32 copy of y, the identity-gradient
+ *                                   accumulator it starts.  y / G may not overlap the inputs or each other (ranges).
+ *                                   Replaces conv2's ReLU + conv backward (network_drrn.py:106-126) */
+int srhip_conv3x3_wgrad_shared_h16_plan(int n, int B, int H, int W, int Cout, int Cin, int* S, long* part_floats_per_item);
+int srhip_conv3x3_wgrad_shared_h16(const srhip_conv_wgrad_h16_item* items, int n, long lddy, long ldx, int B, int H, int W,
+                                   int Cout, int Cin, float* part, int S, int accumulate, void* stream);
+int srhip_conv3x3_dgrad_relu_acc_h16(const void* dY, long lddy, const void* Wht, const void* R, long ldr, void* dX, long lddx,
+                                     float* G, long ldg, int B, int H, int W, int Cout, int Cin, int mode, void* stream);
+int srhip_conv3x3_cin1_h16_flip_mask(const float* x, const float* w, const void* R, long ldr, void* y, long ldy, float* G,
+                                     long ldg, int B, int H, int W, int Co, void* stream);
 /* The MLP half of a Swin block in one kernel per direction (mlp_f16.hip): the hidden activation goes from the first
  * product's accumulators through registers and LDS into the second product and is never read back from HBM.
  *   forward : h = LN(x) . W1^T + b1 (stats[M][2] = {mean, rstd} of x; W1 gamma-folded, b1 beta-folded),

@@ -91,14 +91,31 @@ __device__ __forceinline__ void h16_epilogue(const ConvH16Args& p, const f32x4 (
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * p.alpha;
     }
-    if (p.epi == 9) {                    // data gradient through a ReLU whose fp16 OUTPUT R was kept, times alpha (res_scale)
+    if (p.epi == 9 || p.epi == 10) {     // data gradient through a ReLU whose fp16 OUTPUT R was kept, times alpha (res_scale)
       const h16x8 r = *(const h16x8*)(p.R + pix * p.ldr + col);
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = (float)r[e] > 0.f ? v[e] * p.alpha : 0.f;
     }
+    f32x4 ga = {0.f, 0.f, 0.f, 0.f}, gb = ga;  // epilogues 10 / 11: the f32 identity-gradient accumulator (DRRN's x0)
+    float* gp = nullptr;
+    if (p.epi == 10 || p.epi == 11) {
+      gp = p.G + pix * p.ldg + col;
+      ga = *(const f32x4*)gp; gb = *(const f32x4*)(gp + 4);
+    }
+    if (p.epi == 11) {                   // ... through the same mask, with the accumulated identity gradient added
+      const h16x8 r = *(const h16x8*)(p.R + pix * p.ldr + col);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = (float)r[e] > 0.f ? v[e] * p.alpha + (e < 4 ? ga[e] : gb[e - 4]) : 0.f;
+    }
     h16x8 o;
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = (_Float16)v[e];
+    if (p.epi == 10) {                   // G += the fp16 gradient the chain goes on with (the reference sums fp16 gradients)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { ga[e] += (float)o[e]; gb[e] += (float)o[4 + e]; }
+      *(f32x4*)gp = ga;
+      *(f32x4*)(gp + 4) = gb;
+    }
     if (p.ps) {
       const int fs = p.N >> 2, sp = col / fs, cc = col - sp * fs;
       const long opix = ((long)img * 2 * p.H + 2 * y + (sp >> 1)) * (2 * p.Wd) + 2 * x + (sp & 1);
@@ -670,7 +687,8 @@ __global__ void __launch_bounds__(256, 3) k_srcnn_h16(SrcnnH16Args p) {
 // 1 -> Co conv (f32 image in, fp16 features out), act 0 none | 1 ReLU | 2 LeakyReLU(alpha).  A thread owns 8 output channels of one pixel.
 __global__ void __launch_bounds__(256) k_cin1_h16(const float* __restrict__ x, const float* __restrict__ w,
                                                   const float* __restrict__ bias, _Float16* __restrict__ y, long ldy, int B,
-                                                  int H, int W, int Co, int act, float alpha, int flip) {
+                                                  int H, int W, int Co, int act, float alpha, int flip,
+                                                  const _Float16* __restrict__ mask, long ldm, float* __restrict__ gacc, long ldg) {
   extern __shared__ float wl[];                  // [9][Co] + [Co]
   // flip: w is [1][Co][3][3] (the same bytes as [Co][1][3][3]) read with the taps mirrored -- the data gradient of a Co -> 1 conv
   for (int i = threadIdx.x; i < 9 * Co; i += 256) wl[(flip ? 8 - i % 9 : i % 9) * Co + i / 9] = w[i];
@@ -699,7 +717,17 @@ __global__ void __launch_bounds__(256) k_cin1_h16(const float* __restrict__ x, c
     h16x8 o;
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = (_Float16)(act == 1 ? fmaxf(v[e], 0.f) : (act == 2 && v[e] < 0.f ? v[e] * alpha : v[e]));
+    if (mask) {                                  // the data gradient through a ReLU whose fp16 output was kept (DRRN's r_U)
+      const h16x8 m = *(const h16x8*)(mask + pix * ldm + gq * 8);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = (float)m[e] > 0.f ? o[e] : (_Float16)0.f;
+    }
     *(h16x8*)(y + pix * ldy + gq * 8) = o;
+    if (gacc) {                                  // ... and the f32 identity-gradient accumulator it starts
+      float* const gp = gacc + pix * ldg + gq * 8;
+      *(f32x4*)gp = f32x4{(float)o[0], (float)o[1], (float)o[2], (float)o[3]};
+      *(f32x4*)(gp + 4) = f32x4{(float)o[4], (float)o[5], (float)o[6], (float)o[7]};
+    }
   }
 }
 
@@ -765,8 +793,9 @@ int sr_conv3x3_h16(ConvH16Args& p, hipStream_t st) {
   SR_REQUIRE(p.K % 32 == 0 && p.K >= 32 && p.K <= 4096 && p.N % 64 == 0 && p.N <= 4096,
              "conv3x3_h16: Cin = %d (a multiple of 32), Cout = %d (a multiple of 64), both <= 4096", p.K, p.N);
   SR_REQUIRE(p.ldx % 8 == 0 && p.ldy % 8 == 0 && (!p.R || p.ldr % 8 == 0), "conv3x3_h16: pixel pitches must be multiples of 8 halves");
-  SR_REQUIRE(p.epi == 0 || p.epi == 1 || p.epi == 6 || ((p.epi == 2 || p.epi == 8 || p.epi == 9) && p.R),
-             "conv3x3_h16: epilogue %d (0, 1, 6, 2 / 8 / 9 with R)", p.epi);
+  SR_REQUIRE(p.epi == 0 || p.epi == 1 || p.epi == 6 || ((p.epi == 2 || p.epi == 8 || p.epi == 9) && p.R) ||
+             ((p.epi == 10 || p.epi == 11) && p.R && p.G && p.ldg % 8 == 0 && ((size_t)p.G & 15) == 0 && !p.ps),
+             "conv3x3_h16: epilogue %d (0, 1, 6, 2 / 8 / 9 with R, 10 / 11 with R and a 16-byte aligned G)", p.epi);
   SR_REQUIRE(!p.ps_in || (p.K % 128 == 0 && !p.ps && !p.center_only && !p.in_bn),
              "conv3x3_h16, input through PixelShuffle(2): Cin %% 128 == 0 (Cin=%d), no output shuffle, 3x3, no prologue", p.K);
   SR_REQUIRE(!p.ps_in || (long)p.B * 4 * p.H * p.Wd * p.ldx < (1L << 31),
@@ -803,13 +832,16 @@ int sr_conv3x3_h16(ConvH16Args& p, hipStream_t st) {
 }
 
 int sr_conv_cin1_h16(const float* x, const float* w, const float* bias, void* y, long ldy, int B, int H, int W, int Co, int act,
-                     float alpha, hipStream_t st, int flip) {
+                     float alpha, hipStream_t st, int flip, const _Float16* mask, long ldm, float* G, long ldg) {
   SR_REQUIRE(x && w && y, "conv_cin1_h16: null operand");
   SR_REQUIRE(Co % 8 == 0 && Co <= 1024 && ldy % 8 == 0, "conv_cin1_h16: Cout = %d (a multiple of 8, <= 1024)", Co);
+  SR_REQUIRE((!mask || ldm % 8 == 0) && (!G || (ldg % 8 == 0 && ((size_t)G & 15) == 0)),
+             "conv_cin1_h16: mask / accumulator pitches must be multiples of 8 (G 16-byte aligned)");
   const long n = (long)B * H * W * (Co / 8);
   if (n <= 0) return 0;
   const int grid = (int)(n / 256 + 1 < 8192 ? n / 256 + 1 : 8192);
-  hipLaunchKernelGGL(k_cin1_h16, dim3(grid), dim3(256), (size_t)10 * Co * 4, st, x, w, bias, (_Float16*)y, ldy, B, H, W, Co, act, alpha, flip);
+  hipLaunchKernelGGL(k_cin1_h16, dim3(grid), dim3(256), (size_t)10 * Co * 4, st, x, w, bias, (_Float16*)y, ldy, B, H, W, Co, act, alpha, flip,
+                     mask, ldm, G, ldg);
   SR_LAUNCH_CHECK("k_cin1_h16");
   return 0;
 }

@@ -16,6 +16,8 @@
 //   k_cin1_wgrad_h16   the 1-channel ends: dW[c][t] = sum_p img[p + d_t] feat[p][c] (+ db[c] = sum_p feat[p][c]) of an f32
 //                      image and fp16 features -- the head's weight gradient (image = input, feat = dY) and, with the taps
 //                      mirrored, the tail's (image = dy, feat = the tail's input)
+//                      accumulate: the reducer ADDS into dW / db (DRRN's weights shared by its U residual units: one launch per
+//                      unit, the units in a fixed order -- srhip_conv3x3_wgrad_shared_h16)
 //   k_axpby_h16        y = a y + b x on fp16 (f32 arithmetic): the long skip's gradient add
 //   k_amp_unscale      g *= inv_scale over the flat gradient; a flag when any |g| >= 65520 (an fp16 gradient of the
 //                      reference would be inf) or non-finite before the unscale
@@ -49,6 +51,7 @@ struct WgradH16Args {
   int S, ntiles, tiles_x, tiles_y;
   float* part;                        // [item][S][Cout][9 * Cin + 1]
   long pitem;                         // floats per item
+  int accumulate;                     // 1: the reducer adds into dW / db
 };
 
 __device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c) {
@@ -191,12 +194,14 @@ __global__ void __launch_bounds__(256) k_wgrad_h16_reduce(WgradH16Args p) {
     for (int s = 0; s < p.S; ++s) v += part[(long)s * n + i];
     int co = row;
     if (p.ps2) { const int fs = p.Cout >> 2, sp = row / fs; co = (row - sp * fs) * 4 + sp; }
+    float* dst = nullptr;
     if (k == 9 * p.Cin) {
-      if (p.db[item]) p.db[item][co] = v;
+      if (p.db[item]) dst = p.db[item] + co;
     } else {
       const int t = k / p.Cin, ci = k - t * p.Cin;
-      p.dW[item][((long)co * p.Cin + ci) * 9 + t] = v;
+      dst = p.dW[item] + ((long)co * p.Cin + ci) * 9 + t;
     }
+    if (dst) *dst = p.accumulate ? *dst + v : v;
   }
 }
 
@@ -301,8 +306,25 @@ int srhip_conv3x3_wgrad_h16_plan(int n, int B, int H, int W, int Cout, int Cin, 
   return 0;
 }
 
+// byte ranges [a, a + na) and [b, b + nb) share no byte (NULL or empty ranges share none)
+static bool sr_disjoint(const void* a, long na, const void* b, long nb) {
+  if (!a || !b || na <= 0 || nb <= 0) return true;
+  const char *pa = (const char*)a, *pb = (const char*)b;
+  return pa + na <= pb || pb + nb <= pa;
+}
+// bytes spanned by an NHWC map of `pix` pixels, `c` channels at a pitch of `ld` elements of `es` bytes
+static long sr_map_bytes(long pix, long ld, long c, long es) { return pix > 0 ? ((pix - 1) * ld + c) * es : 0; }
+
+static int sr_wgrad_h16_launch(const srhip_conv_wgrad_h16_item* items, int n, long lddy, long ldx, int B, int H, int W,
+                               int Cout, int Cin, int ps2, float* part, int S, int accumulate, hipStream_t st);
+
 int srhip_conv3x3_wgrad_h16(const srhip_conv_wgrad_h16_item* items, int n, long lddy, long ldx, int B, int H, int W, int Cout,
                             int Cin, int ps2, float* part, int S, void* stream) {
+  return sr_wgrad_h16_launch(items, n, lddy, ldx, B, H, W, Cout, Cin, ps2, part, S, 0, (hipStream_t)stream);
+}
+
+static int sr_wgrad_h16_launch(const srhip_conv_wgrad_h16_item* items, int n, long lddy, long ldx, int B, int H, int W,
+                               int Cout, int Cin, int ps2, float* part, int S, int accumulate, hipStream_t st) {
   SR_REQUIRE(n >= 1 && n <= 40 && items && part && S >= 1, "conv3x3_wgrad_h16: 1..40 problems, workspace, S >= 1");
   SR_REQUIRE(B > 0 && H > 0 && W > 0 && Cout % 64 == 0 && Cin % 64 == 0 && Cout <= 4096 && Cin <= 4096 &&
              (!ps2 || Cout % 256 == 0),
@@ -320,7 +342,7 @@ int srhip_conv3x3_wgrad_h16(const srhip_conv_wgrad_h16_item* items, int n, long 
   p.ntiles = B * p.tiles_y * p.tiles_x;
   p.S = S; p.part = part;
   p.pitem = (long)S * Cout * (9L * Cin + 1);
-  hipStream_t st = (hipStream_t)stream;
+  p.accumulate = accumulate;
   hipLaunchKernelGGL(k_wgrad_h16, dim3(S, (Cout / 64) * (Cin / 64), n), dim3(256), WG_LDS, st, p);
   SR_LAUNCH_CHECK("k_wgrad_h16");
   const long outs = (long)Cout * (9L * Cin + 1);
@@ -379,4 +401,92 @@ int srhip_conv3x3_ps2_bwd_data_h16(const void* dYup, long lddy, const void* Wht,
   p.X = (const _Float16*)dYup; p.ldx = lddy; p.Wb = (const unsigned short*)Wht; p.Y = (_Float16*)dX; p.ldy = ldx;
   p.B = B; p.H = H; p.Wd = W; p.K = Cout; p.N = Cin; p.ps_in = 1; p.alpha = 1.f;
   return sr_conv3x3_h16(p, (hipStream_t)stream);
+}
+
+// ---- DRRN under --amp: the recursion's shared weights and its identity gradient (network_drrn.py:22-126 under autocast,
+// model_plain.py:322-348)
+
+int srhip_conv3x3_wgrad_shared_h16_plan(int n, int B, int H, int W, int Cout, int Cin, int* S, long* part_floats_per_item) {
+  SR_REQUIRE(n >= 1 && n <= 40 && S && part_floats_per_item, "conv3x3_wgrad_shared_h16_plan: 1..40 problems (got %d)", n);
+  SR_REQUIRE(B > 0 && H > 0 && W > 0 && Cout % 64 == 0 && Cin % 64 == 0 && Cout <= 4096 && Cin <= 4096,
+             "conv3x3_wgrad_shared_h16_plan: Cout = %d, Cin = %d (multiples of 64)", Cout, Cin);
+  // a launch is ONE application (two problems for DRRN's unit: 2 x 2 x 2 slices of 128 x 128): the runs alone fill the
+  // GPU -- ~2 blocks per CU (k_wgrad_h16 fits two), at least two tiles a run, at most 64 runs
+  const long ntiles = (long)B * sr_cdiv(H, WG_TR) * sr_cdiv(W, WG_TC);
+  const long slices = (long)n * (Cout / 64) * (Cin / 64);
+  long s = (512 + slices - 1) / slices;
+  if (s > ntiles / 2) s = ntiles / 2;
+  if (s > 64) s = 64;
+  if (s < 1) s = 1;
+  *S = (int)s;
+  *part_floats_per_item = s * Cout * (9L * Cin + 1);
+  return 0;
+}
+
+int srhip_conv3x3_wgrad_shared_h16(const srhip_conv_wgrad_h16_item* items, int n, long lddy, long ldx, int B, int H, int W,
+                                   int Cout, int Cin, float* part, int S, int accumulate, void* stream) {
+  SR_REQUIRE(n >= 1 && n <= 40 && items && part && S >= 1 && S <= 64, "conv3x3_wgrad_shared_h16: 1..40 problems, workspace, S 1..64");
+  SR_REQUIRE(B > 0 && H > 0 && W > 0 && Cout % 64 == 0 && Cin % 64 == 0 && Cout <= 4096 && Cin <= 4096,
+             "conv3x3_wgrad_shared_h16: Cout = %d, Cin = %d (multiples of 64)", Cout, Cin);
+  SR_REQUIRE(lddy % 8 == 0 && ldx % 8 == 0 && lddy >= Cout && ldx >= Cin,
+             "conv3x3_wgrad_shared_h16: pixel pitches (multiples of 8 halves, >= the channels)");
+  // the reducers of a launch run concurrently and read the operands of every problem: no output may overlap another output,
+  // an operand or the workspace (ranges, not base pointers)
+  const long pix = (long)B * H * W;
+  const long bw = (long)Cout * Cin * 9 * 4, bb = (long)Cout * 4;
+  const long bpart = (long)n * S * Cout * (9L * Cin + 1) * 4;
+  for (int k = 0; k < n; ++k) {
+    SR_REQUIRE(items[k].dY && items[k].X && items[k].dW, "conv3x3_wgrad_shared_h16: item %d has a NULL pointer", k);
+    SR_REQUIRE(sr_disjoint(items[k].dW, bw, items[k].db, bb), "conv3x3_wgrad_shared_h16: item %d: dW overlaps db", k);
+    SR_REQUIRE(sr_disjoint(items[k].dW, bw, part, bpart) && sr_disjoint(items[k].db, bb, part, bpart),
+               "conv3x3_wgrad_shared_h16: item %d: an output overlaps the workspace", k);
+    for (int j = 0; j < n; ++j) {
+      const long by = sr_map_bytes(pix, lddy, Cout, 2), bx = sr_map_bytes(pix, ldx, Cin, 2);
+      SR_REQUIRE(sr_disjoint(items[k].dW, bw, items[j].dY, by) && sr_disjoint(items[k].dW, bw, items[j].X, bx) &&
+                 sr_disjoint(items[k].db, bb, items[j].dY, by) && sr_disjoint(items[k].db, bb, items[j].X, bx),
+                 "conv3x3_wgrad_shared_h16: an output of item %d overlaps an operand of item %d", k, j);
+      if (j != k)
+        SR_REQUIRE(sr_disjoint(items[k].dW, bw, items[j].dW, bw) && sr_disjoint(items[k].dW, bw, items[j].db, bb) &&
+                   sr_disjoint(items[k].db, bb, items[j].db, bb),
+                   "conv3x3_wgrad_shared_h16: items %d and %d share an output (one launch per application)", k, j);
+    }
+  }
+  return sr_wgrad_h16_launch(items, n, lddy, ldx, B, H, W, Cout, Cin, 0, part, S, accumulate ? 1 : 0, (hipStream_t)stream);
+}
+
+int srhip_conv3x3_dgrad_relu_acc_h16(const void* dY, long lddy, const void* Wht, const void* R, long ldr, void* dX, long lddx,
+                                     float* G, long ldg, int B, int H, int W, int Cout, int Cin, int mode, void* stream) {
+  SR_REQUIRE(dY && Wht && R && dX && G, "conv3x3_dgrad_relu_acc_h16: null operand");
+  SR_REQUIRE(mode == 0 || mode == 1, "conv3x3_dgrad_relu_acc_h16: mode %d (0 accumulate into G, 1 add G)", mode);
+  SR_REQUIRE(B > 0 && H > 0 && W > 0 && lddy >= Cout && ldr >= Cin && lddx >= Cin && ldg >= Cin,
+             "conv3x3_dgrad_relu_acc_h16: shape / pitches");
+  // dX is written while other tiles still read dY's halo and the epilogue reads R and G; G is read-modify-written
+  const long pix = (long)B * H * W;
+  const long by = sr_map_bytes(pix, lddy, Cout, 2), br = sr_map_bytes(pix, ldr, Cin, 2);
+  const long bx = sr_map_bytes(pix, lddx, Cin, 2), bg = sr_map_bytes(pix, ldg, Cin, 4);
+  SR_REQUIRE(sr_disjoint(dX, bx, dY, by) && sr_disjoint(dX, bx, R, br) && sr_disjoint(dX, bx, G, bg),
+             "conv3x3_dgrad_relu_acc_h16: dX overlaps dY, R or G");
+  SR_REQUIRE(sr_disjoint(G, bg, dY, by) && sr_disjoint(G, bg, R, br), "conv3x3_dgrad_relu_acc_h16: G overlaps dY or R");
+  ConvH16Args p;
+  memset(&p, 0, sizeof(p));
+  p.X = (const _Float16*)dY; p.ldx = lddy; p.Wb = (const unsigned short*)Wht; p.Y = (_Float16*)dX; p.ldy = lddx;
+  p.R = (const _Float16*)R; p.ldr = ldr; p.G = G; p.ldg = ldg; p.epi = mode ? 11 : 10; p.alpha = 1.f;
+  p.B = B; p.H = H; p.Wd = W; p.K = Cout; p.N = Cin;
+  return sr_conv3x3_h16(p, (hipStream_t)stream);
+}
+
+int srhip_conv3x3_cin1_h16_flip_mask(const float* x, const float* w, const void* R, long ldr, void* y, long ldy, float* G,
+                                     long ldg, int B, int H, int W, int Co, void* stream) {
+  SR_REQUIRE(x && w && R && y, "conv3x3_cin1_h16_flip_mask: null operand");
+  SR_REQUIRE(B > 0 && H > 0 && W > 0 && ldr >= Co && ldy >= Co && (!G || ldg >= Co),
+             "conv3x3_cin1_h16_flip_mask: shape / pitches (>= the %d channels)", Co);
+  const long pix = (long)B * H * W;
+  const long by = sr_map_bytes(pix, ldy, Co, 2), br = sr_map_bytes(pix, ldr, Co, 2), bg = sr_map_bytes(pix, ldg, Co, 4);
+  const long bxi = pix * 4, bw = 9L * Co * 4;
+  SR_REQUIRE(sr_disjoint(y, by, R, br) && sr_disjoint(y, by, x, bxi) && sr_disjoint(y, by, w, bw) && sr_disjoint(y, by, G, bg),
+             "conv3x3_cin1_h16_flip_mask: y overlaps an input or G");
+  SR_REQUIRE(sr_disjoint(G, bg, R, br) && sr_disjoint(G, bg, x, bxi) && sr_disjoint(G, bg, w, bw),
+             "conv3x3_cin1_h16_flip_mask: G overlaps an input");
+  return sr_conv_cin1_h16(x, w, nullptr, y, ldy, B, H, W, Co, 0, 0.f, (hipStream_t)stream, 1, (const _Float16*)R, ldr, G,
+                          ldg);
 }

@@ -67,9 +67,11 @@ struct ConvH16Args {
   long plane_bytes; int Kp;          // set by the dispatcher
   const float* bias;                 // [N] (torch order) or null
   _Float16* Y; long ldy;             // NHWC fp16 [B][H][Wd][ldy] (ps: [B][2H][2Wd][ldy], N / 4 channels)
-  const _Float16* R; long ldr;       // residual operand of epilogues 2 / 8
+  const _Float16* R; long ldr;       // residual operand of epilogues 2 / 8, ReLU mask of 9 / 10 / 11
   int epi;                           // 0 +bias | 1 relu | 2 R + alpha*(acc+bias) | 6 leaky relu(alpha) | 8 relu(R + alpha*(acc+bias))
                                      // | 9 R > 0 ? alpha*(acc+bias) : 0 (ReLU mask of the kept output R)
+                                     // | 10 as 9, and G += the stored fp16 value | 11 R > 0 ? alpha*(acc+bias) + G : 0
+  float* G; long ldg;                // f32 accumulator of epilogues 10 / 11 (NHWC [B][H][Wd][ldg])
   float alpha;
   const float* in_bn;                // [4][K] = mean, rstd, gamma*rstd, beta: evaluation-mode BatchNorm + ReLU on the input
   int center_only;                   // 1: only the centre tap is non-zero (a 1x1 conv held as a 3x3 weight)
@@ -79,7 +81,8 @@ struct ConvH16Args {
 };
 int sr_conv3x3_h16(ConvH16Args& p, hipStream_t st);
 int sr_conv_cin1_h16(const float* x, const float* w, const float* bias, void* y, long ldy, int B, int H, int W, int Co, int act,
-                     float alpha, hipStream_t st, int flip = 0);
+                     float alpha, hipStream_t st, int flip = 0, const _Float16* mask = nullptr, long ldm = 0,
+                     float* G = nullptr, long ldg = 0);
 int sr_srcnn_h16(const void* a0, const float* img, int B, int H, int W, const void* W1h, const float* b1, const void* W2h,
                  const float* b2, const float* w3, const float* b3, float* y, long T, hipStream_t st);
 int sr_conv_cout1_h16(const void* x, long ldx, const float* w, const float* bias, const float* add, const float* in_bn, float* y,

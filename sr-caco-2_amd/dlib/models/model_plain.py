@@ -49,8 +49,8 @@ class ModelPlain:
         self.device = torch.device(f'cuda:{dev_id}')
         self.netG = define_G(args).to(self.device)
         # --amp: the reference trains and evaluates under autocast (model_plain.py:322-327); here evaluation takes the
-        # reduced-precision kernels, EDSR trains on fp16 storage (TrainStep(amp=True)), and a TRAINING step of any other net
-        # under --amp raises (optimize_parameters): it is not implemented, and
+        # reduced-precision kernels, EDSR and DRRN train on fp16 storage (TrainStep(amp=True)), and a TRAINING step of any
+        # other net under --amp raises (optimize_parameters): it is not implemented, and
         # training f32-grade under a flag that asks for something else would be a silent change of the run
         self.netG.amp = bool(getattr(args, 'amp', False))
         for k in ('G_regularizer_orthstep', 'G_regularizer_clipstep'):
@@ -202,11 +202,11 @@ class ModelPlain:
         print(f"[libsrhip]{rank} training-step capture failed ({why}): eager steps from here on", flush=True)
 
     # the nets whose engine trains under --amp (fp16 storage + the GradScaler's rules: TrainStep(amp=True))
-    AMP_TRAIN_NETS = ("EDSR_LIIF",)
+    AMP_TRAIN_NETS = ("EDSR_LIIF", "DRRN")
 
     def _amp_train_ok(self):
-        """--amp and an engine with an fp16-storage training path whose configuration it supports (EDSREngine.amp_train_ok);
-        an EDSR the engine cannot take raises here with the reason."""
+        """--amp and an engine with an fp16-storage training path whose configuration it supports (EDSREngine /
+        DRRNEngine.amp_train_ok); an EDSR or DRRN the engine cannot take raises here with the reason."""
         if not getattr(self.netG, 'amp', False):
             return False
         eng = getattr(self.netG, 'engine', None)

@@ -241,7 +241,8 @@ def parse_input(argv=None):
     if cfg['method'] != constants.NETTYPE_METHOD[net_type]:
         raise ValueError(f"--method {cfg['method']} does not match --net_type {net_type} "
                          f"({constants.NETTYPE_METHOD[net_type]})")
-    # --amp True: evaluation (model.test / eval.py) runs the reduced-precision kernels; training stays fp32-accurate
+    # --amp True: evaluation (model.test / eval.py) runs the reduced-precision kernels; EDSR and DRRN train on fp16 storage
+    # under the GradScaler's rules, every other net refuses --amp training
     cfg['netG'] = init_net_g({'net_type': net_type}, cfg)
     if ns.init_pretrained_path is not None:
         cfg['netG']['init_pretrained_path'] = ns.init_pretrained_path

@@ -34,6 +34,7 @@ class DRRNEngine:
         self._prep = self._prep_sig = None
         self.prepared = False
         self.saved = None
+        self.saved_h16 = None           # what forward_h16(save=True) kept for backward_h16
 
     def invalidate(self):
         self.prepared = False
@@ -71,20 +72,47 @@ class DRRNEngine:
         out = F.interpolate(x, size=(s * x.shape[2], s * x.shape[3]), mode='bicubic', align_corners=False)
         return torch.clamp(out, min=0.0, max=1.0)[:, 0].contiguous()
 
-    def forward_h16(self, x):
-        """--amp evaluation on fp16 storage (conv_h16.hip): the same launches with float16 feature maps, one fp16 product."""
+    def amp_train_ok(self):
+        """Whether this configuration trains under --amp on fp16 storage (forward_h16(save=True) + backward_h16): the fp16x2
+        packs of both shared convs in both directions."""
+        if not self.prepared:
+            self.prepare()
+        return self.ws.use_bx3 and all(self.ws[n + s].fmt == 1 for n, _ in self._convs() for s in (".wp", ".wpt"))
+
+    def _amp_train_refusal(self):
+        return (f"DRRN under --amp training runs on fp16 storage only with the fp16x2 packs of both shared convs in both "
+                f"directions; this net: fp16x2 packs {self.ws.use_bx3 and self.ws['wa.wp'].fmt == 1} (SRHIP_MM / "
+                f"SRHIP_F16X2_CONV switch them off)")
+
+    def forward_h16(self, x, save=False):
+        """fp16 storage (conv_h16.hip): the same launches with float16 feature maps, one fp16 product.  save=False: --amp
+        evaluation ("h." buffers, two rotating unit outputs).  save=True: the --amp training forward (autocast's fp16 maps,
+        model_plain.py:322-327): x0 and every unit's a_k, r_{k+1} are kept in "a." buffers of their own -- an evaluation
+        forward in between overwrites none of them."""
+        if not self.prepared:
+            self.prepare()
+        if save and not self.amp_train_ok():
+            raise NotImplementedError(self._amp_train_refusal())
         net, U = self.net, self.U
         xi = self.interpolate(x[:, None])
         B, H, W = xi.shape
+        tag = "a." if save else "h."
 
         def buf(name):
-            return self.bufs.get("h." + name, B, H, W, CH, device=x.device, dtype=torch.float16)
+            return self.bufs.get(tag + name, B, H, W, CH, device=x.device, dtype=torch.float16)
         x0 = ops.conv3x3_cin1_h16(xi, net.conv1[1].weight.data, None, CH, out=buf("x0"), relu=True)
         r = x0
+        rs, as_ = [], []
         for k in range(U):
-            a = ops.conv3x3_h16(r, self.ws["wa.wp"], None, CH, out=buf("a"), epi=1)
-            r = ops.conv3x3_h16(a, self.ws["wb.wp"], None, CH, out=buf(f"r{k % 2}"), epi=8, R=x0)
-        y = ops.conv3x3_cout1_h16(r, net.conv2[1].weight.data, None, add=xi)
+            a = ops.conv3x3_h16(r, self.ws["wa.wp"], None, CH, out=buf(f"a{k}" if save else "a"), epi=1)
+            rs.append(r)
+            as_.append(a)
+            r = ops.conv3x3_h16(a, self.ws["wb.wp"], None, CH, out=buf(f"r{k + 1 if save else k % 2}"), epi=8, R=x0)
+        # (training: the f32 output in the f32 step's own buffer, which ModelPlain.E reads)
+        y = ops.conv3x3_cout1_h16(r, net.conv2[1].weight.data, None, add=xi,
+                                  out=self.bufs.get("t.y", B, H, W, device=x.device) if save else None)
+        if save:
+            self.saved_h16 = dict(xi=xi, x0=x0, rs=rs, as_=as_, r_last=r, B=B, H=H, W=W)
         return y.view(B, 1, H, W)
 
     def forward(self, x, dp=None, save=True):
@@ -164,4 +192,41 @@ class DRRNEngine:
         # single bucket = the last one: TrainStep's reducer sends it after backward (announcing it
         # here too reduced it twice -- the sum instead of the mean -- before the reducer tracked
         # which buckets were done)
+        return None
+
+    def backward_h16(self, dy, grads, need_dx=False, on_layer_done=None, grads_zeroed=False):
+        """backward() on fp16 storage (the reference's backward under autocast: fp16 activation gradients, fp16 products, f32
+        accumulation; model_plain.py:348): dy f32 (the loss gradient, already times the loss scale) -> grads (f32).
+
+        Per unit k = U-1 .. 0, with gu = d / d u_{k+1} (fp16):
+          ga    = (a_k > 0) * conv_b^T(gu)                       conv3x3_h16 epi 9
+          dW_b += gu (x) a_k,  dW_a += ga (x) r_k                one shared-weight weight-gradient launch (unit 0 of the
+                                                                 backward, k = U-1, overwrites; the others add, in order)
+          gu'   = (r_k > 0) * conv_a^T(ga),  G += gu'            k >= 1: the identity gradient into x0 rides in the epilogue
+          g_c1  = (x0 > 0) * (conv_a^T(ga) + G)                  k = 0: r_0 IS x0; the sum ends there
+        G (f32) starts as gu_U from the tail.  The shared weights' gradient is summed in f32 across the units (autograd sums
+        the fp16 per-application gradients of autocast's cached fp16 weight copy in fp16)."""
+        sv = self.saved_h16
+        assert sv is not None, "backward_h16() without a saved forward_h16(save=True)"
+        assert not need_dx, "DRRN (libsrhip): no gradient through the bicubic interpolation of the input"
+        net, U = self.net, self.U
+        B, H, W = sv["B"], sv["H"], sv["W"]
+        dev = dy.device
+
+        def buf(name, dtype=torch.float16):
+            return self.bufs.get("ag." + name, B, H, W, CH, device=dev, dtype=dtype)
+
+        dy = dy.reshape(B, H, W).contiguous()
+        ops.conv3x3_cin1_wgrad_h16(dy, sv["r_last"], grads["conv2.1.weight"], None, flip=True)
+        gus = [buf("gu0"), buf("gu1")]
+        ga, G = buf("ga"), buf("gx0", torch.float32)
+        gu = ops.conv3x3_cin1_h16_flip_mask(dy, net.conv2[1].weight.data, sv["r_last"], gus[U % 2], G)
+        dWa, dWb = grads["trunk.residual_unit.1.weight"], grads["trunk.residual_unit.3.weight"]
+        for k in reversed(range(U)):
+            ops.conv3x3_h16(gu, self.ws["wb.wpt"], None, CH, out=ga, epi=9, R=sv["as_"][k], alpha=1.0)
+            ops.conv3x3_wgrad_shared_h16([(gu, sv["as_"][k], dWb, None), (ga, sv["rs"][k], dWa, None)],
+                                         accumulate=k < U - 1)
+            gu = ops.conv3x3_dgrad_relu_acc_h16(ga, self.ws["wa.wpt"], sv["rs"][k], gus[k % 2], G, mode=0 if k else 1)
+        ops.conv3x3_cin1_wgrad_h16(sv["xi"], gu, grads["conv1.1.weight"], None)
+        # single bucket = the last one: TrainStep's reducer sends it after backward
         return None

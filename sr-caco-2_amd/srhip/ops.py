@@ -1010,6 +1010,81 @@ def conv3x3_cin1_h16_flip(dy, w, Co, out=None):
     return out
 
 
+def conv3x3_wgrad_shared_h16(items, accumulate):
+    """items: (dY float16 NHWC [B,H,W,Cout], X float16 NHWC [B,H,W,Cin], dW [Cout,Cin,3,3] f32, db [Cout] f32 or None) of ONE
+    shape, ONE application of weights that several applications share (srhip_conv3x3_wgrad_shared_h16): accumulate=False:
+    dW = this application's weight gradient, True: dW += it.  Called once per application in a fixed order, the sum is
+    deterministic.  The items' outputs must be distinct tensors."""
+    dY0, X0 = items[0][0], items[0][1]
+    B, H, W, Cin = X0.shape
+    Cout = items[0][2].shape[0]
+    n = len(items)
+    assert 1 <= n <= 40 and tuple(dY0.shape) == (B, H, W, Cout)
+    S = ctypes.c_int(0)
+    per = ctypes.c_long(0)
+    call("srhip_conv3x3_wgrad_shared_h16_plan", n, B, H, W, Cout, Cin, ctypes.addressof(S), ctypes.addressof(per))
+    part = SCRATCH.get("wgsh16_part", n * per.value, device=dY0.device)
+    arr = (_ConvWgradH16Item * n)()
+    for k, (dY, X, dW, db) in enumerate(items):
+        _chk(dW, db)
+        assert dY.shape == dY0.shape and X.shape == X0.shape and dY.is_contiguous() and X.is_contiguous()
+        assert dW.is_contiguous() and tuple(dW.shape) == (Cout, Cin, 3, 3)
+        arr[k].dY, arr[k].X, arr[k].dW, arr[k].db = _ph(dY), _ph(X), _p(dW), _p(db)
+
+    def run():
+        call("srhip_conv3x3_wgrad_shared_h16", ctypes.addressof(arr), n, dY0.stride(2), X0.stride(2), B, H, W, Cout, Cin,
+             _p(part), S.value, int(bool(accumulate)), _st())
+    if probe.on("conv_tn_h16"):
+        T = B * H * W
+        with probe.timed(("conv_tn_h16", f"shared x{n}", T, Cout, Cin), 18.0 * T * Cout * Cin * n,
+                         2.0 * n * (T * Cin + T * Cout) + 4.0 * n * S.value * Cout * (9 * Cin + 1) * 2):
+            run()
+    else:
+        run()
+
+
+def conv3x3_dgrad_relu_acc_h16(dY, Wpt, R, out, G, mode):
+    """The data gradient of a conv behind a ReLU whose fp16 output R was kept, with an f32 identity-gradient accumulator G
+    (srhip_conv3x3_dgrad_relu_acc_h16): dY float16 [B,H,W,Cout], Wpt the fp16x2 data-gradient pack -> out float16
+    [B,H,W,Cin].  mode 0: out = (R > 0) * acc, G += out; mode 1: out = (R > 0) * (acc + G)."""
+    assert isinstance(Wpt, Bx3) and Wpt.fmt == 1, "conv3x3_dgrad_relu_acc_h16: fp16x2 weight planes"
+    B, H, W, Cout = dY.shape
+    Cin = out.shape[3]
+    assert Wpt.rows == 9 * Cin and Wpt.K == Cout and tuple(out.shape) == (B, H, W, Cin)
+    assert tuple(R.shape) == tuple(out.shape) and tuple(G.shape) == tuple(out.shape) and G.dtype == torch.float32
+    assert dY.stride(3) == 1 and R.stride(3) == 1 and out.stride(3) == 1 and G.stride(3) == 1
+    assert dY.stride(1) == W * dY.stride(2) and R.stride(1) == W * R.stride(2) and out.stride(1) == W * out.stride(2)
+    assert G.stride(1) == W * G.stride(2)
+    _chk(G)
+
+    def run():
+        call("srhip_conv3x3_dgrad_relu_acc_h16", _ph(dY), dY.stride(2), _p(Wpt.planes), _ph(R), R.stride(2), _ph(out),
+             out.stride(2), _p(G), G.stride(2), B, H, W, Cout, Cin, int(mode), _st())
+    if probe.on("conv_h16"):
+        T = B * H * W
+        with probe.timed(("conv_h16", f"dgrad_relu_acc{int(mode)}", T, Cin, Cout), 18.0 * T * Cout * Cin,
+                         2.0 * (T * Cout + 2 * T * Cin) + 4.0 * T * Cin * (2 - int(mode)) + 18.0 * Cin * Cout):
+            run()
+    else:
+        run()
+    return out
+
+
+def conv3x3_cin1_h16_flip_mask(dy, w, R, out, G=None):
+    """The tail's data gradient through the ReLU in front of it (srhip_conv3x3_cin1_h16_flip_mask): f32 dy [B,H,W] through the
+    mirrored taps of w [1,Co,3,3], zero where R <= 0 (R float16 [B,H,W,Co]) -> out float16 [B,H,W,Co]; G (f32 [B,H,W,Co] or
+    None) = out as f32."""
+    _chk(dy, w, G)
+    B, H, W = dy.shape
+    Co = out.shape[3]
+    assert dy.is_contiguous() and w.is_contiguous() and w.numel() == 9 * Co
+    assert tuple(R.shape) == tuple(out.shape) == (B, H, W, Co) and R.stride(3) == 1 and out.stride(3) == 1
+    assert G is None or (tuple(G.shape) == (B, H, W, Co) and G.stride(3) == 1 and G.dtype == torch.float32)
+    call("srhip_conv3x3_cin1_h16_flip_mask", _p(dy), _p(w), _ph(R), R.stride(2), _ph(out), out.stride(2), _p(G),
+         0 if G is None else G.stride(2), B, H, W, Co, _st())
+    return out
+
+
 def axpby_h16(y, x, a, b):
     """y = a y + b x on float16 tensors of one size (f32 arithmetic)."""
     assert y.is_contiguous() and x.is_contiguous() and y.numel() == x.numel()
