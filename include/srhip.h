@@ -835,9 +835,10 @@ int srhip_conv3x3_wgrad_batched_bx3(const srhip_conv_wgrad_item* items, int n, l
 /* ---- optimizers (dlib/utils/utils_instance.py:216-247) on flat buffers -------
  * g is multiplied by gscale first (1/world_size after a sum all-reduce).  If
  * skip_flag != NULL and *skip_flag != 0 the update is skipped on the device
- * (non-finite loss, model_plain.py:344-346) -- no host sync. */
-int srhip_adam_step(float* p, const float* g, float* m, float* v, long n, int step, float lr, float b1,
-                    float b2, float eps, float wd, float gscale, const int* skip_flag, void* stream);
+ * (non-finite loss, model_plain.py:344-346) -- no host sync.  Adam's betas are the Python floats (double): the kernels use
+ * (float)beta and (float)(1.0 - beta) and the bias corrections 1 - beta^step taken in double, as torch.optim.Adam does. */
+int srhip_adam_step(float* p, const float* g, float* m, float* v, long n, int step, float lr, double b1,
+                    double b2, float eps, float wd, float gscale, const int* skip_flag, void* stream);
 int srhip_sgd_step(float* p, const float* g, float* buf, long n, float lr, float momentum, float wd,
                    int nesterov, int first, float gscale, const int* skip_flag, void* stream);
 /* The same updates with the step number kept ON THE DEVICE: srhip_optim_tick does
@@ -850,7 +851,7 @@ int srhip_sgd_step(float* p, const float* g, float* buf, long n, float lr, float
  * schedule (MyStepLR, utils_trainer.py:370). */
 int srhip_optim_tick(const int* skip_flag, int* counter, void* stream);
 int srhip_adam_step_dc(float* p, const float* g, float* m, float* v, long n, const int* counter, float lr,
-                       float b1, float b2, float eps, float wd, float gscale, const int* skip_flag,
+                       double b1, double b2, float eps, float wd, float gscale, const int* skip_flag,
                        const float* lr_dev, void* stream);
 int srhip_sgd_step_dc(float* p, const float* g, float* buf, long n, const int* counter, float lr,
                       float momentum, float wd, int nesterov, float gscale, const int* skip_flag,
@@ -865,9 +866,11 @@ long srhip_grad_norm_clip_ws(void);
 int srhip_grad_norm_clip(float* g, long n, float gscale, float max_norm, float* norm_coef, void* workspace,
                          long workspace_bytes, void* stream);
 /* Exponential moving average of the weights, ModelBase.update_E (model_base.py:213-219; E_decay > 0, model_plain.py:393-394):
- * e = e * decay + p * (1 - decay) over the flat parameter buffer.  Skipped on the device when *skip_flag != 0 (the
- * reference returns from the step before update_E on a non-finite loss, model_plain.py:344-346). */
-int srhip_ema_update(float* e, const float* p, long n, float decay, const int* skip_flag, void* stream);
+ * e = e * decay + p * (1 - decay) over the flat parameter buffer, in the reference's f32 arithmetic: decay is the Python
+ * float, and the kernel uses (float)decay and (float)(1.0 - decay), as e.mul_(decay).add_(p, alpha=1-decay) does.  Skipped on
+ * the device when *skip_flag != 0 (the reference returns from the step before update_E on a non-finite loss,
+ * model_plain.py:344-346). */
+int srhip_ema_update(float* e, const float* p, long n, double decay, const int* skip_flag, void* stream);
 /* ---- data-parallel gradient exchange (comm.hip): what DistributedDataParallel's reducer does for the reference
  * (dlib/models/model_base.py:135-142), for a caller that is not PyTorch.  One process per GPU; one communicator per process
  * (RCCL over xGMI; resolved with dlopen at the first call -- the copy PyTorch bundles if the process has one, else ROCm's

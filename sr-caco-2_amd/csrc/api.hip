@@ -301,7 +301,14 @@ int srhip_resblock64_fwd_f16x2(const float* x, long ldx, const void* W1h, const 
   SR_REQUIRE(x && W1h && b1 && W2h && b2 && a && out, "resblock64_fwd: null operand");
   SR_REQUIRE(ldx % 4 == 0 && lda % 4 == 0 && ldout % 4 == 0 && ldx >= 64 && lda >= 64 && ldout >= 64,
              "resblock64_fwd: pixel pitches must be multiples of 4 floats, >= 64");
-  SR_REQUIRE(out != x && a != x, "resblock64_fwd: out / a must not alias x (neighbouring tiles read its halo)");
+  {
+    // neighbouring tiles read x's halo after a tile has stored a / out, and the weight gradient reads a behind the launch: the
+    // three maps share no byte (an offset view into one buffer included)
+    const long pix = (long)B * H * W, bx = sr_map_bytes(pix, ldx, 64, 4), ba = sr_map_bytes(pix, lda, 64, 4),
+               bo = sr_map_bytes(pix, ldout, 64, 4);
+    SR_REQUIRE(sr_disjoint(out, bo, x, bx) && sr_disjoint(a, ba, x, bx), "resblock64_fwd: out / a overlap x");
+    SR_REQUIRE(sr_disjoint(out, bo, a, ba), "resblock64_fwd: out overlaps a (the saved activation)");
+  }
   SR_REQUIRE((long)B * H * W * ldx < (1L << 30), "resblock64_fwd: input beyond 4 GB");
   SR_REQUIRE(sr_matmul_mode() == 0, "resblock64_fwd: f32-accurate matmul mode only");
   ResBlockArgs p;
@@ -315,7 +322,14 @@ int srhip_resblock64_bwd_f16x2(const float* g, long ldg, const void* W2Th, const
   SR_REQUIRE(g && W2Th && W1Th && a && da && dx, "resblock64_bwd: null operand");
   SR_REQUIRE(ldg % 4 == 0 && lda % 4 == 0 && ldda % 4 == 0 && lddx % 4 == 0 && ldg >= 64 && lda >= 64 && ldda >= 64 && lddx >= 64,
              "resblock64_bwd: pixel pitches must be multiples of 4 floats, >= 64");
-  SR_REQUIRE(dx != g && da != g && da != a, "resblock64_bwd: dx / da must not alias g, da must not alias a");
+  {
+    // g and a are only read (they may share bytes); every written map is disjoint from every other map
+    const long pix = (long)B * H * W, bg = sr_map_bytes(pix, ldg, 64, 4), ba = sr_map_bytes(pix, lda, 64, 4),
+               bda = sr_map_bytes(pix, ldda, 64, 4), bdx = sr_map_bytes(pix, lddx, 64, 4);
+    SR_REQUIRE(sr_disjoint(dx, bdx, g, bg) && sr_disjoint(dx, bdx, a, ba), "resblock64_bwd: dx overlaps g or a");
+    SR_REQUIRE(sr_disjoint(da, bda, g, bg) && sr_disjoint(da, bda, a, ba), "resblock64_bwd: da overlaps g or a");
+    SR_REQUIRE(sr_disjoint(da, bda, dx, bdx), "resblock64_bwd: da overlaps dx");
+  }
   SR_REQUIRE((long)B * H * W * ldg < (1L << 30), "resblock64_bwd: input beyond 4 GB");
   SR_REQUIRE(sr_matmul_mode() == 0, "resblock64_bwd: f32-accurate matmul mode only");
   ResBlockArgs p;

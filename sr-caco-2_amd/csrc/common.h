@@ -20,6 +20,15 @@ int sr_fail(int code, const char* fmt, ...);
   do { hipError_t e_ = hipGetLastError(); \
        if (e_ != hipSuccess) return sr_fail(-5, "%s: %s", name, hipGetErrorString(e_)); } while (0)
 
+// byte ranges [a, a + na) and [b, b + nb) share no byte (NULL or empty ranges share none): the aliasing checks of the entry points
+static inline bool sr_disjoint(const void* a, long na, const void* b, long nb) {
+  if (!a || !b || na <= 0 || nb <= 0) return true;
+  const char *pa = (const char*)a, *pb = (const char*)b;
+  return pa + na <= pb || pb + nb <= pa;
+}
+// bytes spanned by an NHWC map of `pix` pixels, `c` channels at a pitch of `ld` elements of `es` bytes
+static inline long sr_map_bytes(long pix, long ld, long c, long es) { return pix > 0 ? ((pix - 1) * ld + c) * es : 0; }
+
 // Tuning and ablation switches are read from the environment only by builds made with `make EXPERIMENTS=1`
 // (-DSRHIP_EXPERIMENTS; tools/ab_*.sh load such a build through SRHIP_LIB): the shipped library takes its defaults.
 #ifdef SRHIP_EXPERIMENTS

@@ -306,15 +306,6 @@ int srhip_conv3x3_wgrad_h16_plan(int n, int B, int H, int W, int Cout, int Cin, 
   return 0;
 }
 
-// byte ranges [a, a + na) and [b, b + nb) share no byte (NULL or empty ranges share none)
-static bool sr_disjoint(const void* a, long na, const void* b, long nb) {
-  if (!a || !b || na <= 0 || nb <= 0) return true;
-  const char *pa = (const char*)a, *pb = (const char*)b;
-  return pa + na <= pb || pb + nb <= pa;
-}
-// bytes spanned by an NHWC map of `pix` pixels, `c` channels at a pitch of `ld` elements of `es` bytes
-static long sr_map_bytes(long pix, long ld, long c, long es) { return pix > 0 ? ((pix - 1) * ld + c) * es : 0; }
-
 static int sr_wgrad_h16_launch(const srhip_conv_wgrad_h16_item* items, int n, long lddy, long ldx, int B, int H, int W,
                                int Cout, int Cin, int ps2, float* part, int S, int accumulate, hipStream_t st);
 

@@ -682,8 +682,11 @@ __global__ void __launch_bounds__(1024) k_sum_partials(const double* __restrict_
 // ----------------------------------------------------------------------------
 // optimizers on the flat parameter buffer (utils_instance.py:216-247)
 // ----------------------------------------------------------------------------
+// Adam as torch.optim.Adam computes it on f32 tensors: betas and (1 - beta) are the Python floats' values rounded to f32 each
+// (1 - beta taken in double: (float)(1 - 0.999) = 0.001, not 1 - (float)0.999 = 0.000999987), the bias corrections are
+// 1 - beta^step in double (adam.py: bias_correction1 / bias_correction2 ** 0.5) rounded once
 __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                       float* __restrict__ v, long n, float lr, float b1, float b2, float eps,
+                       float* __restrict__ v, long n, float lr, float b1, float b2, float omb1, float omb2, float eps,
                        float wd, float bc1, float bc2_sqrt, float gscale, const int* __restrict__ skip) {
   if (skip && *skip) return;   // non-finite loss: skip the update (model_plain.py:344-346)
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n;
@@ -691,8 +694,8 @@ __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float
     float gi = g[i] * gscale;
     const float pi = p[i];
     if (wd != 0.f) gi += wd * pi;
-    const float mi = m[i] * b1 + (1.f - b1) * gi;
-    const float vi = v[i] * b2 + (1.f - b2) * gi * gi;
+    const float mi = m[i] * b1 + omb1 * gi;
+    const float vi = v[i] * b2 + omb2 * gi * gi;
     m[i] = mi; v[i] = vi;
     const float denom = sqrtf(vi) / bc2_sqrt + eps;
     p[i] = pi - (lr / bc1) * (mi / denom);
@@ -723,21 +726,23 @@ __global__ void k_optim_tick(const int* __restrict__ skip, int* __restrict__ cou
   if (threadIdx.x == 0 && blockIdx.x == 0 && !(skip && *skip)) *counter += 1;
 }
 __global__ void k_adam_dc(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                          float* __restrict__ v, long n, const int* __restrict__ counter, float lr, float b1,
-                          float b2, float eps, float wd, float gscale, const int* __restrict__ skip,
+                          float* __restrict__ v, long n, const int* __restrict__ counter, float lr, double b1d,
+                          double b2d, float eps, float wd, float gscale, const int* __restrict__ skip,
                           const float* __restrict__ lr_dev) {
   if (skip && *skip) return;
   if (lr_dev) lr = *lr_dev;       // learning rate from device memory: a captured launch replays with the current one
-  const float step = (float)*counter;
-  const float bc1 = 1.f - powf(b1, step);
-  const float bc2_sqrt = sqrtf(1.f - powf(b2, step));
+  // k_adam's constants, the bias corrections from the device-side step count
+  const double step = (double)*counter;
+  const float b1 = (float)b1d, b2 = (float)b2d, omb1 = (float)(1.0 - b1d), omb2 = (float)(1.0 - b2d);
+  const float bc1 = (float)(1.0 - pow(b1d, step));
+  const float bc2_sqrt = (float)sqrt(1.0 - pow(b2d, step));
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n;
        i += (long)gridDim.x * blockDim.x) {
     float gi = g[i] * gscale;
     const float pi = p[i];
     if (wd != 0.f) gi += wd * pi;
-    const float mi = m[i] * b1 + (1.f - b1) * gi;
-    const float vi = v[i] * b2 + (1.f - b2) * gi * gi;
+    const float mi = m[i] * b1 + omb1 * gi;
+    const float vi = v[i] * b2 + omb2 * gi * gi;
     m[i] = mi; v[i] = vi;
     const float denom = sqrtf(vi) / bc2_sqrt + eps;
     p[i] = pi - (lr / bc1) * (mi / denom);
@@ -801,13 +806,15 @@ __global__ void k_scale_dev(float* __restrict__ g, long n, const float* __restri
   if (c == 1.f) return;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) g[i] *= c;
 }
-// exponential moving average of the weights (ModelBase.update_E, model_base.py:213-219): e = e * decay + p * (1 - decay);
-// skipped with the optimizer update on a non-finite loss (optimize_parameters returns before update_E, model_plain.py:344-346)
+// exponential moving average of the weights (ModelBase.update_E, model_base.py:213-219): e.mul_(decay).add_(p, alpha=1-decay),
+// torch's arithmetic on f32 tensors: the product e * decay rounded, then p * alpha added by one fused multiply-add (the
+// vectorised add with alpha); skipped with the optimizer update on a non-finite loss (optimize_parameters returns before
+// update_E, model_plain.py:344-346)
 __global__ void k_ema(float* __restrict__ e, const float* __restrict__ p, long n, float decay, float alpha,
                       const int* __restrict__ skip) {
   if (skip && *skip) return;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-    e[i] = __fadd_rn(__fmul_rn(e[i], decay), __fmul_rn(p[i], alpha));
+    e[i] = __fmaf_rn(p[i], alpha, __fmul_rn(e[i], decay));
 }
 // finite check: flag[0] |= any(!isfinite(x))
 __global__ void k_nonfinite(const float* __restrict__ x, long n, int* __restrict__ flag) {
@@ -1058,13 +1065,14 @@ int srhip_sum(const float* x, long n, float* out, double* workspace, void* strea
   return 0;
 }
 
-int srhip_adam_step(float* p, const float* g, float* m, float* v, long n, int step, float lr, float b1,
-                    float b2, float eps, float wd, float gscale, const int* skip_flag, void* stream) {
+int srhip_adam_step(float* p, const float* g, float* m, float* v, long n, int step, float lr, double b1,
+                    double b2, float eps, float wd, float gscale, const int* skip_flag, void* stream) {
   if (n <= 0) return 0;
-  const float bc1 = 1.f - powf(b1, (float)step);
-  const float bc2 = 1.f - powf(b2, (float)step);
+  const double bc1 = 1.0 - pow(b1, (double)step);
+  const double bc2 = 1.0 - pow(b2, (double)step);
   hipLaunchKernelGGL(k_adam, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr,
-                     b1, b2, eps, wd, bc1, sqrtf(bc2), gscale, skip_flag);
+                     (float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), eps, wd, (float)bc1, (float)sqrt(bc2),
+                     gscale, skip_flag);
   SR_LAUNCH_CHECK("adam_step");
   return 0;
 }
@@ -1086,7 +1094,7 @@ int srhip_optim_tick(const int* skip_flag, int* counter, void* stream) {
 }
 
 int srhip_adam_step_dc(float* p, const float* g, float* m, float* v, long n, const int* counter, float lr,
-                       float b1, float b2, float eps, float wd, float gscale, const int* skip_flag,
+                       double b1, double b2, float eps, float wd, float gscale, const int* skip_flag,
                        const float* lr_dev, void* stream) {
   if (n <= 0) return 0;
   SR_REQUIRE(counter != nullptr, "adam_step_dc: counter is NULL");
@@ -1124,12 +1132,13 @@ int srhip_grad_norm_clip(float* g, long n, float gscale, float max_norm, float* 
   return 0;
 }
 
-int srhip_ema_update(float* e, const float* p, long n, float decay, const int* skip_flag, void* stream) {
+int srhip_ema_update(float* e, const float* p, long n, double decay, const int* skip_flag, void* stream) {
   if (n <= 0) return 0;
   SR_REQUIRE(e && p, "ema_update: null operand");
-  SR_REQUIRE(decay >= 0.f && decay <= 1.f, "ema_update: decay = %g outside [0, 1]", (double)decay);
-  hipLaunchKernelGGL(k_ema, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, e, p, n, decay,
-                     (float)(1.0 - (double)decay), skip_flag);
+  SR_REQUIRE(decay >= 0.0 && decay <= 1.0, "ema_update: decay = %g outside [0, 1]", decay);
+  // the reference's two constants: the Python float decay and 1 - decay (taken in double), each rounded to f32 by the op
+  hipLaunchKernelGGL(k_ema, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, e, p, n, (float)decay,
+                     (float)(1.0 - decay), skip_flag);
   SR_LAUNCH_CHECK("ema_update");
   return 0;
 }

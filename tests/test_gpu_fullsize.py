@@ -37,7 +37,9 @@ def sub(d, prefix):
 def need_gpu():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    torch.set_num_threads(min(32, os.cpu_count() or 1))
+    # the oracle's host threads: the process's budget (OMP_NUM_THREADS, else torch's own setting), never the box's core count
+    env = os.environ.get("OMP_NUM_THREADS", "")
+    torch.set_num_threads(min(32, int(env) if env.isdigit() and int(env) > 0 else torch.get_num_threads()))
 
 
 def rel_err(a, ref):

@@ -660,6 +660,90 @@ def test_grad_norm_clip_and_ema_kernels(ops):
         ops.grad_norm_clip(dev(gr), 1.0, 0.0, nc)             # max_norm must be positive
 
 
+def test_ema_update_at_the_reference_decay_over_many_steps(ops):
+    """srhip_ema_update at E_decay = 0.999 over 3,000 steps from e = 0 (a 4 MB flat buffer), against the reference's
+    constants: update_E does e.mul_(decay).add_(p, alpha=1-decay) (model_base.py:213-219), so the op multiplies by
+    float32(0.999) and adds float32(1 - 0.999) with 1 - decay taken in double.  A kernel that derives the second constant
+    from the float-rounded decay is 1.3e-5 relative off it, and netE follows that gain.
+    Gates: the least-squares gain of the kernel's e over the fp64 recurrence with the reference's two constants within 1e-6
+    (the constant), and the kernel within 3e-6 of max|p| of the reference's own f32 op sequence (O.ema_update on the host:
+    the product e * decay rounded, the add with alpha fused).  The f32 recurrence itself moves up to ~3e-5 of max|p| away
+    from the exact one at this decay (rounding of e * decay, 1000 steps of memory), so the exact value bounds it only to
+    twice the reference's own distance."""
+    n = 1 << 20
+    gen = torch.Generator().manual_seed(77)
+    p = torch.randn(n, generator=gen) * 0.05
+    decay = 0.999
+    d32 = float(torch.tensor(decay, dtype=torch.float32))
+    a32 = float(torch.tensor(1.0 - decay, dtype=torch.float32))
+    e, pd = torch.zeros(n).cuda(), dev(p)
+    ref = torch.zeros(n)
+    exact, p64 = torch.zeros(n, dtype=torch.float64), p.double()
+    for _ in range(3000):
+        ops.ema_update(e, pd, decay)
+        O.ema_update([ref], [p], decay)
+        exact.mul_(d32).add_(p64, alpha=a32)
+    ec, refd = e.cpu().double(), ref.double()
+    pm = p.abs().max().item()
+    gain = ((ec - exact) * exact).sum().item() / (exact * exact).sum().item()
+    e_ref = (ec - refd).abs().max().item() / pm
+    e_exact = (ec - exact).abs().max().item() / pm
+    own = (refd - exact).abs().max().item() / pm
+    print(f"\nEMA 0.999 x 3000: gain vs the exact recurrence {gain:.2e}; max vs the reference's f32 ops {e_ref:.2e}; "
+          f"max vs exact {e_exact:.2e} (the reference's own f32: {own:.2e})")
+    assert abs(gain) <= 1e-6, gain
+    assert e_ref <= 3e-6, e_ref
+    assert e_exact <= 2.0 * own + 1e-7, (e_exact, own)
+    # a short leg from a non-zero netE at both decays of the suite: the reference's f32 ops on the host
+    for dc in (0.999, 0.9):
+        e0 = rnd(4096)
+        p1 = rnd(4096)
+        e, eo = dev(e0), [e0.clone()]
+        for _ in range(20):
+            ops.ema_update(e, dev(p1), dc)
+            O.ema_update(eo, [p1], dc)
+        assert (e.cpu() - eo[0]).abs().max() <= 1.2e-7 * eo[0].abs().max(), dc
+
+
+def test_resblock64_refuses_aliased_maps(ops):
+    """srhip_resblock64_{fwd,bwd}_f16x2 refuse maps that share bytes where one of them is written -- the same base or an
+    offset view into one buffer: a forward whose out overlapped a would overwrite the saved activation the weight gradient
+    reads, a backward whose da overlapped dx would mix the two data gradients.  Reads may overlap (g and a)."""
+    from srhip._lib import SrhipError
+    if not ops.resblock64_fusable(64):
+        pytest.skip("fp16x2 conv operands are off")
+    B, H, W, C = 2, 8, 16, 64
+    N = B * H * W * C
+    planes = {k: ops.Bx3(9 * C, C, "cuda") for k in ("w1", "w2", "w1t", "w2t")}
+    w1d, w2d = dev(rnd(C, C, 3, 3, scale=0.05)), dev(rnd(C, C, 3, 3, scale=0.05))
+    tb = ops.PrepTable()
+    tb.conv(w1d, planes["w1"])
+    tb.conv(w2d, planes["w2"])
+    tb.conv(w1d, planes["w1t"], data_grad=True)
+    tb.conv(w2d, planes["w2t"], data_grad=True)
+    tb.build("cuda").run()
+    b1, b2 = dev(rnd(C, scale=0.3)), dev(rnd(C, scale=0.3))
+    pool = torch.zeros(4 * N).cuda()
+
+    def at(px):                         # an NHWC map starting px pixels into the pool
+        return pool[px * C:px * C + N].view(B, H, W, C)
+    x, a, out = at(0), at(N // C), at(2 * N // C)
+    fwd = lambda x_, a_, o_: ops.resblock64_fwd(x_, planes["w1"], b1, planes["w2"], b2, 1.0, a_, o_)
+    bwd = lambda g_, a_, da_, dx_: ops.resblock64_bwd(g_, planes["w2t"], planes["w1t"], a_, 1.0, da_, dx_)
+    half = N // C // 2
+    for args in ((x, x, out), (x, a, x), (x, a, a),                                # identical bases
+                 (x, at(half), out), (x, a, at(half)), (x, a, at(N // C + 1))):     # partial overlaps
+        with pytest.raises(SrhipError):
+            fwd(*args)
+    g, da, dx = at(0), at(2 * N // C), at(3 * N // C)
+    for args in ((g, a, da, da), (g, a, da, g), (g, a, a, dx), (g, a, da, a),      # identical bases
+                 (g, a, da, at(2 * N // C + half)), (g, a, at(half), dx), (g, a, da, at(N // C + 3))):
+        with pytest.raises(SrhipError):
+            bwd(*args)
+    bwd(g, g, da, dx)                   # g and a are only read: sharing them is allowed
+    torch.cuda.synchronize()
+
+
 def test_errors_are_loud(ops):
     with pytest.raises(RuntimeError):
         ops.gemm_nt(torch.zeros(4, 6).cuda(), torch.zeros(4, 6).cuda())       # K % 4 != 0
