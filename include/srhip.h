@@ -396,8 +396,9 @@ int srhip_conv3x3_wgrad(const float* dY, long lddy, const float* X, long ldx, in
 /* The three weight-gradient contractions above on the bf16 MFMA with 3-way split
  * operands (see srhip_gemm_nt_bx3): same arguments, alignment rules, slicing and
  * reducers; plan S with the _bx3 planners (one 8-wave block per CU).  The 3x3 conv forms with Cout and Cin multiples of
- * 64 (three taps per block) split their operands into TWO fp16 planes under a running power-of-two scale per operand
- * column and issue three products -- same f32-grade sums; SRHIP_TN_F16X2=0 in the environment: three bf16 planes, six.
+ * 64, one of them 64 (all nine taps per block), and the single conv problems on 128- / 192-column tiles (not the
+ * PixelShuffle form) split their operands into TWO fp16 planes under a running power-of-two scale per operand column and
+ * issue three products -- same f32-grade sums.
  * Round 6: 3x3 conv problems of at least 64 channels on either side, on images whose width is a multiple of 64, run in the
  * strip form (all nine taps per block, power-of-two scales fixed per block, a second pass for the blocks whose guess did not
  * hold); part_floats of the conv plan is the partial sums [S][9][NI][NJ] PLUS that kernel's per-block words behind them --

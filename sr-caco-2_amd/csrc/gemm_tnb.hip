@@ -111,7 +111,7 @@ template <> struct ColVec<3> {
   static __device__ __forceinline__ float at(T v, int j) { return v[j]; }
 };
 
-template <int W, int DBG = 0>     // DBG (timing experiments, env SRHIP_TN_DBG): 1 no MFMA, 2 no producer work
+template <int W>
 __device__ __forceinline__ void tnb_body(const TnArgs& p, const int s, const int tile, const int tap,
                                          unsigned char* smem) {
   constexpr int BC = 64 * W;                 // columns per operand tile
@@ -306,15 +306,6 @@ __device__ __forceinline__ void tnb_body(const TnArgs& p, const int s, const int
     }
   };
 
-  auto touch = [&](const Stage& sg) __attribute__((always_inline)) {   // DBG 4: the column maxima of a stage, thrown away
-    float mx = 0.f;
-#pragma unroll
-    for (int t = 0; t < 16; ++t)
-#pragma unroll
-      for (int j = 0; j < W; ++j) mx = fmaxf(mx, fabsf(ColVec<W>::at(sg.rv[t >> 3][t & 7], j)));
-    asm volatile("" ::"v"(mx));
-  };
-
   f32x16 acc[W][W];
 #pragma unroll
   for (int i = 0; i < W; ++i)
@@ -348,66 +339,48 @@ __device__ __forceinline__ void tnb_body(const TnArgs& p, const int s, const int
     store(smem, sg0);
     load(m_begin + 2 * TKB, sg0);
     __syncthreads();
-    long t_store = 0, t_load = 0, t_bar = 0;      // DBG 3: s_memtime stamps of the producer phases
     for (int c = 0; c < nch; c += 2) {
-      const long s0 = DBG == 3 ? (long)__builtin_amdgcn_s_memtime() : 0;
-      if (DBG != 2) store(smem + BUF, sg1);                 // chunk c+1
-      const long s1 = DBG == 3 ? (long)__builtin_amdgcn_s_memtime() : 0;
-      if (DBG != 2) load(m_begin + (c + 3) * TKB, sg1);
-      if (DBG == 4) touch(sg0);                  // experiment: chunk c+2 must have landed one half-iteration early
-      const long s2 = DBG == 3 ? (long)__builtin_amdgcn_s_memtime() : 0;
+      store(smem + BUF, sg1);                   // chunk c+1
+      load(m_begin + (c + 3) * TKB, sg1);
       __syncthreads();
-      const long s3 = DBG == 3 ? (long)__builtin_amdgcn_s_memtime() : 0;
-      if (DBG != 2) {
-        store(smem, sg0);                       // chunk c+2
-        load(m_begin + (c + 4) * TKB, sg0);
-      }
-      if (DBG == 4) touch(sg1);
+      store(smem, sg0);                         // chunk c+2
+      load(m_begin + (c + 4) * TKB, sg0);
       __syncthreads();
-      if (DBG == 3) { t_store += s1 - s0; t_load += s2 - s1; t_bar += s3 - s2; }
-    }
-    if (DBG == 3 && blockIdx.x == 0 && tile == 0 && lane == 0) {   // cycles per chunk, by producer wave
-      float* o = p.part + wave * 4;
-      o[0] = (float)t_store / (nch / 2); o[1] = (float)t_load / (nch / 2); o[2] = (float)t_bar / (nch / 2);
-      o[3] = (float)nch;
     }
   } else {
     __syncthreads();
     for (int c = 0; c < nch; ++c) {
       const unsigned char* cur = smem + (c & 1) * BUF;
-      if (DBG != 1) {
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          u32x4 fa[W][3];
+      for (int ks = 0; ks < 2; ++ks) {
+        u32x4 fa[W][3];
 #pragma unroll
-          for (int i = 0; i < W; ++i)
+        for (int i = 0; i < W; ++i)
 #pragma unroll
-            for (int pl = 0; pl < 3; ++pl) fa[i][pl] = *(const u32x4*)(cur + pl * PLANE + a_off[i][ks]);
+          for (int pl = 0; pl < 3; ++pl) fa[i][pl] = *(const u32x4*)(cur + pl * PLANE + a_off[i][ks]);
 #pragma unroll
-          for (int j = 0; j < W; ++j) {
-            u32x4 fb0 = *(const u32x4*)(cur + b_off[j][ks]);
-            u32x4 fb1 = *(const u32x4*)(cur + PLANE + b_off[j][ks]);
-            u32x4 fb2 = *(const u32x4*)(cur + 2 * PLANE + b_off[j][ks]);
+        for (int j = 0; j < W; ++j) {
+          u32x4 fb0 = *(const u32x4*)(cur + b_off[j][ks]);
+          u32x4 fb1 = *(const u32x4*)(cur + PLANE + b_off[j][ks]);
+          u32x4 fb2 = *(const u32x4*)(cur + 2 * PLANE + b_off[j][ks]);
 #pragma unroll
-            for (int i = 0; i < W; ++i) acc[i][j] = mfma_bf(fa[i][1], fb1, acc[i][j]);
+          for (int i = 0; i < W; ++i) acc[i][j] = mfma_bf(fa[i][1], fb1, acc[i][j]);
 #pragma unroll
-            for (int i = 0; i < W; ++i) acc[i][j] = mfma_bf(fa[i][0], fb2, acc[i][j]);
+          for (int i = 0; i < W; ++i) acc[i][j] = mfma_bf(fa[i][0], fb2, acc[i][j]);
 #pragma unroll
-            for (int i = 0; i < W; ++i) acc[i][j] = mfma_bf(fa[i][2], fb0, acc[i][j]);
+          for (int i = 0; i < W; ++i) acc[i][j] = mfma_bf(fa[i][2], fb0, acc[i][j]);
 #pragma unroll
-            for (int i = 0; i < W; ++i) acc[i][j] = mfma_bf(fa[i][0], fb1, acc[i][j]);
+          for (int i = 0; i < W; ++i) acc[i][j] = mfma_bf(fa[i][0], fb1, acc[i][j]);
 #pragma unroll
-            for (int i = 0; i < W; ++i) acc[i][j] = mfma_bf(fa[i][1], fb0, acc[i][j]);
+          for (int i = 0; i < W; ++i) acc[i][j] = mfma_bf(fa[i][1], fb0, acc[i][j]);
 #pragma unroll
-            for (int i = 0; i < W; ++i) acc[i][j] = mfma_bf(fa[i][0], fb0, acc[i][j]);
-          }
+          for (int i = 0; i < W; ++i) acc[i][j] = mfma_bf(fa[i][0], fb0, acc[i][j]);
         }
       }
       __syncthreads();
     }
 
   float* out = p.part + ((long)(s * (p.conv ? 9 : 1) + tap) * p.NI) * p.NJ;
-  if (DBG == 3) return;     // stamp build: keep the stamps in part[]
 #pragma unroll
   for (int i = 0; i < W; ++i)
 #pragma unroll
@@ -440,8 +413,18 @@ __device__ __forceinline__ void tnb_body(const TnArgs& p, const int s, const int
 }
 
 // ---------------------------------------------------------------------------
-// Linear problems (conv == 0) on TWO fp16 planes and three products: the scheme of tnb_body3<.., true> in the general
-// tile.  A column's scale must be ONE value for its 32-token chunk, and in tnb_body the two token halves of a column are
+// The operands as TWO fp16 planes and three products (h*h + h*l + l*h on v_mfma_f32_32x32x16_f16) instead of three bf16
+// planes and six.  fp16 has 5 exponent bits, so every operand COLUMN (a channel of dY or of X) carries a power-of-two scale
+// 2^s: the producer lane that owns the column keeps it as a running value that only goes down -- when a chunk's largest |x|
+// would pass 60000 after scaling, s drops so that the maximum lands in [8192, 16384] and the lane posts the (exact,
+// power-of-two) factor next to the chunk's planes; the consumers multiply their accumulators by factor(row) *
+// factor(column) before that chunk's MFMAs (a wave-uniform branch on four flag words; rare after the first chunks).  The
+// epilogue multiplies by 2^-s(row) * 2^-s(column).  An element far below its column's maximum keeps an ABSOLUTE error of
+// 2^-25 in scaled units = 2^-39 of the column maximum: the sum over tokens -- what a weight gradient is -- stays f32-grade
+// (error <= ~2^-22 * sum |a| |b|), which per-column scaling could not give an NT product.
+//
+// Linear problems (conv == 0) in the general tile.  A column's scale must be ONE value for its 32-token chunk, and in
+// tnb_body the two token halves of a column are
 // staged by different waves -- so the producer roles are re-cut here: wave = operand x COLUMN half (32 W columns), lane =
 // column W-tuple (lane & 31) x token half (lane >> 5).  The two halves of a column sit in lanes l and l ^ 32 of one
 // wave: one cross-lane exchange per column and chunk gives both the same maximum, both keep the same running
@@ -569,7 +552,8 @@ __device__ __forceinline__ void tnb_body_h(const TnArgs& p, const int s, const i
   // (Experiments, dropped.  The next chunk's loads issued in the MIDDLE of store(), right after the values have left the stage
   // registers, so that they fly under 1.6 store() periods: with the exact waits of load_i 460-473 -> 536-540 us per launch on
   // the README net -- the data then returns into the register file while the producer is busiest; issued at the end of
-  // store() it returns while the wave sits at the barrier.  The same move in tnb_body / tnb_body3: 1-2.5 % of the step lost.
+  // store() it returns while the wave sits at the barrier.  The same move in tnb_body and in the three-tap conv body of
+  // round 5 (since removed): 1-2.5 % of the step lost.
   // THREE register stages over the two LDS buffers (a load gets almost three chunk periods): the LayerNorm instantiation
   // needs more than the 256 registers two waves per SIMD leave -- 169 spills, and scratch traffic shares vmcnt with the
   // prefetch.  The launch WITHOUT any operand prologue (no LayerNorm / DropPath arithmetic: wrong results, same accesses):
@@ -822,284 +806,12 @@ __device__ __forceinline__ void tnb_body_h(const TnArgs& p, const int s, const i
 }
 
 // ---------------------------------------------------------------------------
-// 64-wide conv problems, THREE taps (one kernel row dy) per block.  With one tap per block a 64 x 64 tile gives a
-// consumer wave 12 MFMAs per 32-token chunk and barrier while the producers load and split 128 columns for it, and
-// every tap block splits the same dY tile again (23 % of the bf16x3 rate on the EDSR shapes).  Here the dY tile of a
-// chunk is staged ONCE for the three taps dx = -1, 0, +1 (the three shifted X tiles each get their own LDS image: a
-// token octet must be 16-byte aligned for the MFMA operand) in 16-TOKEN chunks: four operand tiles x 16 tokens = one
-// staging job per producer wave (wave k stages operand k: dY, X(-1), X(0), X(+1)), 18 MFMAs per consumer wave and
-// barrier, 48 KB of LDS -- three blocks per CU as before.  (The same with 32-token chunks -- 36 MFMAs per barrier,
-// 96 KB, ONE block per CU -- measured 4.5 % SLOWER than one tap per block: eight waves per CU do not hide the
-// producers' load latency.)  Plain operands only (no prologue, no row scale), NI and NJ multiples of 64.
-// ---------------------------------------------------------------------------
-constexpr int TK3 = 16;                         // tokens per chunk = one k step of the 32x32x16 MFMA
-#define SR_TNB3_OCC 6                           // waves per SIMD: three 8-wave blocks per CU
-__device__ __forceinline__ int unit_slot3(int col, int u) { return 2 * col + (u ^ ((col >> 3) & 1)); }
-
+// 64-wide conv problems, ALL NINE taps per block (round 6; two fp16 planes / three products only, with the running column
+// scales of tnb_body_h).
 //
-// F16: the operands as TWO fp16 planes and three products (h*h + h*l + l*h on v_mfma_f32_32x32x16_f16) instead of three
-// bf16 planes and six.  fp16 has 5 exponent bits, so every operand COLUMN (a channel of dY or of X) carries a power-of-two
-// scale 2^s: the producer lane that owns the column keeps it as a running value that only goes down -- when a chunk's
-// largest |x| would pass 60000 after scaling, s drops so that the maximum lands in [8192, 16384] and the lane posts the
-// (exact, power-of-two) factor next to the chunk's planes; the consumers multiply their accumulators by factor(row) *
-// factor(column) before that chunk's MFMAs (a wave-uniform branch on four flag words; rare after the first chunks).  The
-// epilogue multiplies by 2^-s(row) * 2^-s(column).  An element far below its column's maximum keeps an ABSOLUTE error of
-// 2^-25 in scaled units = 2^-39 of the column maximum: the sum over tokens -- what a weight gradient is -- stays
-// f32-grade (error <= ~2^-22 * sum |a| |b|), which per-column scaling could not give an NT product.
-template <int DBG = 0, bool F16 = false>
-__device__ __forceinline__ void tnb_body3(const TnArgs& p, const int s, const int tile, const int trow,
-                                          unsigned char* smem) {
-  constexpr int BC = 64, NOP = 4;              // operand tiles per chunk: dY, X(dx = -1), X(0), X(+1)
-  constexpr int PLANE = NOP * BC * 32;         // bytes per plane per chunk buffer (two 16-byte token octets per column)
-  constexpr int BUF = 3 * PLANE;
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave8 = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const bool producer = wave8 >= 4;
-  const int wave = wave8 & 3;
-  const int wi = wave >> 1, wj = wave & 1, r = lane & 31, h = lane >> 5;
-  const int nbj = p.NJ / BC;
-  const int bi = tile / nbj, bj = tile - bi * nbj;
-  const int i0 = bi * BC, j0 = bj * BC;
-  const int m_begin = s * p.rows_per_slice;
-  const int m_end = min(p.M, m_begin + p.rows_per_slice);
-  const int dy = trow - 1;
-  const bool do_colsum = p.part_colsum && bj == 0 && trow == 0;
-
-  struct Stage { float rv[2][8]; };            // 16 tokens x this lane's column in flight
-  const int op = wave;                         // producer wave k stages operand tile k
-  const bool isB = op != 0;
-  const int ps_f = p.NI >> 2;
-  unsigned colb = (unsigned)lane * 4u;
-  if (!isB && p.ps) {
-    const int ig = i0 + lane, sp = ig / ps_f, cc = ig - sp * ps_f;
-    colb = (unsigned)((((sp >> 1) * 2 * p.Wd + (sp & 1)) * (int)p.lda + cc) * 4);
-  }
-  const float* const P = isB ? p.B + j0 : (p.ps ? p.A : p.A + i0);      // uniform
-  const long ld = isB ? p.ldb : p.lda;
-  const int step = (!isB && p.ps) ? 2 : 1;
-  float cs = 0.f;
-  float sc = 0x1p126f;                         // F16: this lane's column scale ("unset": any non-zero chunk sets it)
-  constexpr int CTRL = 2 * PLANE;              // F16: per chunk buffer, in the place of the third plane: factors [4][64], flags [4]
-  constexpr int SINV = 2 * PLANE + 2048;       // F16: final 2^-s [4][64] (buffer 0)
-
-  auto load = [&](int mc, Stage& sg) __attribute__((always_inline)) {
-    const int gm = mc + (lane & 15);             // token of this lane's per-token data
-    const bool in = gm < m_end;
-    const int x = gm % p.Wd, tq = gm / p.Wd;
-    const int y = tq % p.H, b = tq / p.H;
-    int srow = gm;
-    bool ok = in;
-    if (isB) {
-      const int yy = y + dy, xx = x + op - 2;
-      ok = ok && yy >= 0 && yy < p.H && xx >= 0 && xx < p.Wd;
-      srow = (b * p.H + yy) * p.Wd + xx;
-    } else if (p.ps) {
-      srow = (b * 2 * p.H + 2 * y) * 2 * p.Wd + 2 * x;
-    }
-    const int t_row = ok ? srow : -1;
-    const int row0 = __builtin_amdgcn_readlane(t_row, 0);
-    const bool dense = __all(t_row == row0 + step * (lane & 15) && row0 >= 0);
-    if (dense) {
-      const float* q = P + (long)row0 * ld;
-      const long adv = step * ld;
-#pragma unroll
-      for (int t = 0; t < 16; ++t) {
-        sg.rv[t >> 3][t & 7] = ColVec<1>::ldg(q, colb);
-        q += adv;
-      }
-    } else {
-#pragma unroll
-      for (int t = 0; t < 16; ++t) {
-        const int row = __builtin_amdgcn_readlane(t_row, t);
-        const float* base = row >= 0 ? P + (long)row * ld : k_tnb_zero_row;
-        sg.rv[t >> 3][t & 7] = ColVec<1>::ldg(base, row >= 0 ? colb : 0u);
-      }
-    }
-  };
-  auto store = [&](unsigned char* buf, const Stage& sg) __attribute__((always_inline)) {
-    if constexpr (F16) {
-      float mx = 0.f;
-#pragma unroll
-      for (int t = 0; t < 16; ++t) mx = fmaxf(mx, fabsf(sg.rv[t >> 3][t & 7]));
-      float f = 1.f;
-      if (mx * sc > 60000.f) {
-        const float ns = exp2f(fminf(floorf(log2f(16384.f / mx)), 120.f));
-        f = ns / sc;
-        sc = ns;
-      }
-      const bool ch = __any(f != 1.f);
-      float* ctrl = (float*)(buf + CTRL);
-      if (ch) ctrl[op * BC + lane] = f;
-      if (lane == 0) ((int*)(ctrl + NOP * BC))[op] = ch ? 1 : 0;
-#pragma unroll
-      for (int o = 0; o < 2; ++o) {
-        unsigned qh[4], ql[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const float e0 = sg.rv[o][2 * t], e1 = sg.rv[o][2 * t + 1];
-          if (do_colsum) cs += e0 + e1;            // read by the dY wave only
-          split2_pair(e0 * sc, e1 * sc, qh[t], ql[t]);
-        }
-        unsigned char* dst = buf + unit_slot3(op * BC + lane, o) * 16;
-        *(u32x4*)(dst) = u32x4{qh[0], qh[1], qh[2], qh[3]};
-        *(u32x4*)(dst + PLANE) = u32x4{ql[0], ql[1], ql[2], ql[3]};
-      }
-      return;
-    }
-#pragma unroll
-    for (int o = 0; o < 2; ++o) {
-      unsigned qh[4], qm[4], ql[4];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const float e0 = sg.rv[o][2 * t], e1 = sg.rv[o][2 * t + 1];
-        if (do_colsum) cs += e0 + e1;              // read by the dY wave only
-        split3_pair(e0, e1, qh[t], qm[t], ql[t]);
-      }
-      const u32x4 ph = {qh[0], qh[1], qh[2], qh[3]}, pm = {qm[0], qm[1], qm[2], qm[3]},
-                  pl = {ql[0], ql[1], ql[2], ql[3]};
-      unsigned char* dst = buf + unit_slot3(op * BC + lane, o) * 16;
-      *(u32x4*)(dst) = ph;
-      *(u32x4*)(dst + PLANE) = pm;
-      *(u32x4*)(dst + 2 * PLANE) = pl;
-    }
-  };
-
-  f32x16 acc[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc[k][q] = 0.f;
-  const int a_off = unit_slot3(wi * 32 + r, h) * 16;
-  int b_off[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) b_off[k] = unit_slot3((1 + k) * BC + wj * 32 + r, h) * 16;
-
-  // (Round 6, measured and dropped: THREE register stages -- a chunk's rows requested three chunk periods ahead.  The role
-  // ablations say the staging path is the longer pole (tools/mb_tnb3.py at 8 x 256 x 256, 64 -> 256 channels: all 960 us | no
-  // MFMAs 739 | no staging 538), but the third stage does not fit: 127 spilled registers at the 80 of three blocks per CU, 50
-  // at the 128 of two -- scratch traffic shares vmcnt with the prefetch: EDSR x8 1,810 -> 1,143 patches/s.)
-  const int nch = ((m_end - m_begin + 2 * TK3 - 1) / (2 * TK3)) * 2;     // even
-  if (producer) {
-    __builtin_amdgcn_s_setprio(2);                    // staging waves first: they are the critical path of a chunk
-    Stage sg0, sg1;                              // chunk parity
-    load(m_begin, sg0);
-    load(m_begin + TK3, sg1);
-    store(smem, sg0);
-    load(m_begin + 2 * TK3, sg0);
-    __syncthreads();
-    for (int c = 0; c < nch; c += 2) {
-      if (DBG != 2 && DBG != 5) {
-        store(smem + BUF, sg1);                  // chunk c+1
-        load(m_begin + (c + 3) * TK3, sg1);
-      }
-      __syncthreads();
-      if (DBG != 2 && DBG != 5) {
-        store(smem, sg0);                        // chunk c+2
-        load(m_begin + (c + 4) * TK3, sg0);
-      }
-      __syncthreads();
-    }
-    if constexpr (F16) {
-      ((float*)(smem + SINV))[op * BC + lane] = 1.0f / sc;
-      __syncthreads();
-    }
-  } else {
-    __syncthreads();
-    u32x4 g5[8];
-    if (DBG == 5) {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) g5[q] = *(const u32x4*)(smem + q * 1024 + lane * 16);
-    }
-    for (int c = 0; c < nch; ++c) {
-      const unsigned char* cur = smem + (c & 1) * BUF;
-      if constexpr (F16) {
-        if (DBG != 1) {
-          const float* ctrl = (const float*)(cur + CTRL);
-          const u32x4 fl = *(const u32x4*)(ctrl + NOP * BC);
-          if (__builtin_amdgcn_readfirstlane(fl.x | fl.y | fl.z | fl.w)) {       // some column's scale dropped with this chunk: bring the sums along
-            float fa_[16];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) fa_[q] = fl.x ? ctrl[wi * 32 + mfma_row(q, lane)] : 1.f;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-              const unsigned on = k == 0 ? fl.y : (k == 1 ? fl.z : fl.w);
-              const float fb = on ? ctrl[(1 + k) * BC + wj * 32 + r] : 1.f;
-#pragma unroll
-              for (int q = 0; q < 16; ++q) acc[k][q] *= fa_[q] * fb;
-            }
-          }
-          // DBG 5 (experiments): no fragment reads -- the operands are whatever the registers of `g5` hold (read once in front
-          // of the loop): what remains per chunk is the flag word, nine MFMAs and the barrier
-          const u32x4 ah = DBG == 5 ? g5[0] : *(const u32x4*)(cur + a_off), al = DBG == 5 ? g5[1] : *(const u32x4*)(cur + PLANE + a_off);
-#pragma unroll
-          for (int k = 0; k < 3; ++k) {
-            const u32x4 bh = DBG == 5 ? g5[2 + k] : *(const u32x4*)(cur + b_off[k]);
-            const u32x4 bl = DBG == 5 ? g5[5 + k] : *(const u32x4*)(cur + PLANE + b_off[k]);
-            acc[k] = mfma_h(al, bh, acc[k]);
-            acc[k] = mfma_h(ah, bl, acc[k]);
-            acc[k] = mfma_h(ah, bh, acc[k]);
-          }
-        }
-        __syncthreads();
-        continue;
-      }
-      if (DBG != 1) {
-        u32x4 fa[3];
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) fa[pl] = *(const u32x4*)(cur + pl * PLANE + a_off);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          const u32x4 fb0 = *(const u32x4*)(cur + b_off[k]);
-          const u32x4 fb1 = *(const u32x4*)(cur + PLANE + b_off[k]);
-          const u32x4 fb2 = *(const u32x4*)(cur + 2 * PLANE + b_off[k]);
-          acc[k] = mfma_bf(fa[1], fb1, acc[k]);
-          acc[k] = mfma_bf(fa[0], fb2, acc[k]);
-          acc[k] = mfma_bf(fa[2], fb0, acc[k]);
-          acc[k] = mfma_bf(fa[0], fb1, acc[k]);
-          acc[k] = mfma_bf(fa[1], fb0, acc[k]);
-          acc[k] = mfma_bf(fa[0], fb0, acc[k]);
-        }
-      }
-      __syncthreads();
-    }
-    const int col = wj * 32 + r;
-    if constexpr (F16) {
-      __syncthreads();                             // the producers' final 2^-s
-      const float* sinv = (const float*)(smem + SINV);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const float ib = sinv[(1 + k) * BC + col];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[k][q] *= sinv[wi * 32 + mfma_row(q, lane)] * ib;
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      float* out = p.part + ((long)(s * 9 + 3 * trow + k) * p.NI) * p.NJ;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int io = i0 + wi * 32 + mfma_row(q, lane);       // p.ps: kernel row sp*F + c is torch channel c*4 + sp
-        out[(long)(p.ps ? (io % ps_f) * 4 + io / ps_f : io) * p.NJ + j0 + col] = acc[k][q];
-      }
-    }
-  }
-
-  if (do_colsum) {
-    float* red = (float*)smem;                   // the chunk buffers are dead now
-    if (producer && op == 0) red[lane] = cs;
-    __syncthreads();
-    if (tid < BC) {
-      const int io = i0 + tid;
-      p.part_colsum[(long)s * p.NI + (p.ps ? (io % ps_f) * 4 + io / ps_f : io)] = red[tid];
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// 64-wide conv problems, ALL NINE taps per block (round 6; two fp16 planes / three products only).
-//
-// What the three-tap form costs (role ablations, tools/mb_tnb3.py, 8 x 256 x 256 pixels, 64 -> 256 channels: everything
+// It replaced the THREE-tap form of round 5 (since removed): one block per kernel row dy staged, in 16-token chunks, the dY
+// tile once and the three X tiles shifted by dx = -1, 0, +1 each into an LDS image of its own, three 8-wave blocks per CU.
+// What that form cost (role ablations, tools/mb_tnb3.py, 8 x 256 x 256 pixels, 64 -> 256 channels: everything
 // 960 us | consumers without their MFMAs 739 | producers without loads and stores 538 -- against 186 us of matrix time):
 //   * staging: a tap row's block stages dY and three shifted X tiles for its three taps -- twelve operand tiles per chunk
 //     position for the nine taps, every one split (VALU) and written to LDS, and the staging waves run at the latency of their
@@ -1112,8 +824,13 @@ __device__ __forceinline__ void tnb_body3(const TnArgs& p, const int s, const in
 // (one operand tile each, THREE register stages: a chunk's rows are requested three chunk periods ahead) and eight matrix
 // waves = 2 x 2 quadrants of the 64 x 64 tile x two tap groups (taps 0-4 / 5-8: 15 + 12 MFMAs per SIMD and chunk, the same
 // on all four SIMDs); a matrix wave reads ten fragments (three dY shifts, two X rows; 10 KB) for 15 / 12 MFMAs.  Partial
-// sums leave in the layout of the three-tap form ([slice][tap][NI][NJ]): same reducers.
+// sums leave in the layout of the one-tap form (tnb_body: [slice][tap][NI][NJ]): same reducers.
+//
+// LDS: per plane and column two 16-byte units (token octets 0, 1 of a 16-token chunk), unit (col, u) at slot
+// 2 col + (u ^ bit 3 of col).
 // ---------------------------------------------------------------------------
+constexpr int TK9 = 16;                         // tokens per chunk = one k step of the 32x32x16 MFMA
+__device__ __forceinline__ int unit_slot9(int col, int u) { return 2 * col + (u ^ ((col >> 3) & 1)); }
 constexpr int T9_OPS = 6;
 constexpr int T9_PLANE = T9_OPS * 64 * 32;        // bytes per plane and chunk buffer
 constexpr int T9_CTRL = 2 * T9_PLANE;             // factors [6][64] floats, then the six flag words (+ 2 pad)
@@ -1139,9 +856,9 @@ __device__ __forceinline__ void tnb9_consume(const TnArgs& p, const int s, const
     for (int q = 0; q < 16; ++q) acc[u][q] = 0.f;
   int a_off[3], b_off[2];
 #pragma unroll
-  for (int d = 0; d < 3; ++d) a_off[d] = unit_slot3(d * 64 + wi * 32 + r, h) * 16;
+  for (int d = 0; d < 3; ++d) a_off[d] = unit_slot9(d * 64 + wi * 32 + r, h) * 16;
 #pragma unroll
-  for (int d = 0; d < 2; ++d) b_off[d] = unit_slot3((3 + DY0 + d) * 64 + wj * 32 + r, h) * 16;
+  for (int d = 0; d < 2; ++d) b_off[d] = unit_slot9((3 + DY0 + d) * 64 + wj * 32 + r, h) * 16;
   __syncthreads();
   long long ts0 = 0, ts1 = 0;
   if (DBG == 3) ts0 = (long long)wall_clock64();
@@ -1231,7 +948,7 @@ __device__ __forceinline__ void tnb_body9(const TnArgs& p, const int s, const in
   const int i0 = bi * BC, j0 = bj * BC;
   const int m_begin = s * p.rows_per_slice;
   const int m_end = min(p.M, m_begin + p.rows_per_slice);
-  const int nch = ((m_end - m_begin + 3 * TK3 - 1) / (3 * TK3)) * 3;      // a multiple of 3: three register stages
+  const int nch = ((m_end - m_begin + 3 * TK9 - 1) / (3 * TK9)) * 3;      // a multiple of 3: three register stages
   if (!producer) {
     const int q4 = wave & 3;
     if (wave < 4) tnb9_consume<0, DBG>(p, s, i0, j0, nch, smem, q4 >> 1, q4 & 1, lane);
@@ -1345,7 +1062,7 @@ __device__ __forceinline__ void tnb_body9(const TnArgs& p, const int s, const in
         if (do_colsum) cs += e0 + e1;
         split2_pair(e0 * sc, e1 * sc, qh[t], ql[t]);
       }
-      unsigned char* dst = buf + unit_slot3(op * BC + lane, o) * 16;
+      unsigned char* dst = buf + unit_slot9(op * BC + lane, o) * 16;
       *(u32x4*)(dst) = u32x4{qh[0], qh[1], qh[2], qh[3]};
       *(u32x4*)(dst + T9_PLANE) = u32x4{ql[0], ql[1], ql[2], ql[3]};
     }
@@ -1353,15 +1070,15 @@ __device__ __forceinline__ void tnb_body9(const TnArgs& p, const int s, const in
   __builtin_amdgcn_s_setprio(2);
   Stage sa, sb, sc3;
   load(m_begin, sa);
-  load(m_begin + TK3, sb);
-  load(m_begin + 2 * TK3, sc3);
+  load(m_begin + TK9, sb);
+  load(m_begin + 2 * TK9, sc3);
   if (lane == 0 && op == 0) { int* fw = (int*)(smem + T9_CTRL) + T9_OPS * BC; fw[6] = 0; fw[7] = 0; fw = (int*)(smem + T9_BUF + T9_CTRL) + T9_OPS * BC; fw[6] = 0; fw[7] = 0; }
   store(smem, sa);
-  load(m_begin + 3 * TK3, sa);
+  load(m_begin + 3 * TK9, sa);
   __syncthreads();
   // chunk c + K + 1 goes to buffer (c + K + 1) & 1 from the stage that holds it; that stage then takes chunk c + K + 4
 #define SR_T9STEP(K_, ST_)                                                                                   \
-  if (DBG != 2 && DBG < 7) { store(smem + (((c + (K_) + 1) & 1) ? T9_BUF : 0), ST_); load(m_begin + (c + (K_) + 4) * TK3, ST_); } \
+  if (DBG != 2 && DBG < 7) { store(smem + (((c + (K_) + 1) & 1) ? T9_BUF : 0), ST_); load(m_begin + (c + (K_) + 4) * TK9, ST_); } \
   if (DBG != 8 && DBG != 10) __syncthreads();
 #pragma unroll 1
   for (int c = 0; c < nch; c += 3) {
@@ -1449,9 +1166,9 @@ __device__ __forceinline__ void tnb9s_consume(const TnArgs& p, const int s, cons
                                               const int nsteps, unsigned char* smem, const int wi, const int wj, const int lane) {
   const int r = lane & 31, h = lane >> 5;
   f32x16 acc[3];
-  const int a_self = unit_slot3(wi * 32 + r, h) * 16;                     // + c * S9_SUB: the lane's octet 2 c + h of chunk c
+  const int a_self = unit_slot9(wi * 32 + r, h) * 16;                     // + c * S9_SUB: the lane's octet 2 c + h of chunk c
   const int a_edge = S9_DYE + h * 256 + (wi * 32 + r) * 4;                // + c * 512: edge tokens of octet 2 c + h - 1, + 512: 2 c + h + 1
-  const int b_self = unit_slot3(wj * 32 + r, h) * 16;
+  const int b_self = unit_slot9(wj * 32 + r, h) * 16;
   {
 #pragma unroll
     for (int u = 0; u < 3; ++u)
@@ -1615,7 +1332,7 @@ __device__ __forceinline__ void tnb_body9s(const TnArgs& p, const int s, const i
         if (!isB) cs += e0 + e1;
         split2_pair(e0 * sc, e1 * sc, qh[t], ql[t]);
       }
-      unsigned char* dst = rb + (o >> 1) * S9_SUB + unit_slot3(lane, o & 1) * 16;
+      unsigned char* dst = rb + (o >> 1) * S9_SUB + unit_slot9(lane, o & 1) * 16;
       *(u32x4*)(dst) = u32x4{qh[0], qh[1], qh[2], qh[3]};
       *(u32x4*)(dst + PL) = u32x4{ql[0], ql[1], ql[2], ql[3]};
       if (!isB) {                                  // the octet's edge tokens: first | last << 16
@@ -1705,14 +1422,6 @@ __global__ void __launch_bounds__(S9_THREADS) k_tnb9s(TnArgs p, int tiles, int x
   tnb_body9s<DBG>(p, L / tiles, L % tiles, tiles, PASS, smem);
 }
 
-template <int DBG = 0, bool F16 = false>
-__global__ void __launch_bounds__(512, SR_TNB3_OCC) k_tnb3(TnArgs p, int tiles, int xcd) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int L = xcd ? sr_xcd_block(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-  const int trow = L % 3, t2 = L / 3;
-  tnb_body3<DBG, F16>(p, t2 / tiles, t2 % tiles, trow, smem);
-}
-
 // Conv launches are one-dimensional with the block -> (slice, tile, tap) map made here: the 9 taps x i-tiles of one
 // slice read the same rows of dY and X, and the hardware deals consecutive block indices to the 8 XCDs round robin --
 // with (slice, tile, tap) on the grid axes every XCD's L2 fetched every slice for itself (rocprofv3 PMC: 2.5 GB per
@@ -1766,7 +1475,7 @@ __device__ __forceinline__ void tnb_group_block(const TnbGroup& g, int& slice, i
     t = blockIdx.x / g.S;
   }
 }
-template <int W, int DBG = 0>
+template <int W>
 __global__ void __launch_bounds__(512, 1) k_tnb_grouped(TnbGroup g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   int slice, t;
@@ -1776,7 +1485,7 @@ __global__ void __launch_bounds__(512, 1) k_tnb_grouped(TnbGroup g) {
 #pragma unroll
   for (int i = 1; i < TNB_GROUP_MAX; ++i)
     if (i < g.n && t >= g.tile_start[i]) { p = g.p[i]; t0 = g.tile_start[i]; }
-  tnb_body<W, DBG>(p, slice, t - t0, 0, smem);
+  tnb_body<W>(p, slice, t - t0, 0, smem);
 }
 
 template <int W>
@@ -1829,22 +1538,6 @@ __global__ void __launch_bounds__(512, 1) k_tnb_conv_batched(TnbConvBatch g) {
   tnb_body<W>(p, sl, tile, tap, smem);
 }
 
-template <int DBG = 0, bool F16 = false>
-__global__ void __launch_bounds__(512, SR_TNB3_OCC) k_tnb3_conv_batched(TnbConvBatch g) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int L = g.xcd ? sr_xcd_block(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-  const int trow = L % 3;
-  int rr = L / 3;
-  const int tile = rr % g.tiles; rr /= g.tiles;
-  const int sl = rr % g.base.S, k = rr / g.base.S;
-  TnArgs p = g.base;
-  p.A = g.A[k];
-  p.B = g.B[k];
-  p.part = g.base.part + (long)k * g.part_stride;
-  p.part_colsum = g.base.part_colsum ? g.base.part_colsum + (long)k * g.colsum_stride : nullptr;
-  tnb_body3<DBG, F16>(p, sl, tile, trow, smem);
-}
-
 __global__ void __launch_bounds__(T9_THREADS) k_tnb9_conv_batched(TnbConvBatch g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int L = g.xcd ? sr_xcd_block(blockIdx.x, gridDim.x) : (int)blockIdx.x;
@@ -1877,31 +1570,6 @@ __global__ void __launch_bounds__(S9_THREADS) k_tnb9s_conv_batched(TnbConvBatch 
   one(g.xcd ? sr_xcd_block(blockIdx.x, gridDim.x) : (int)blockIdx.x);
 }
 
-// three taps per block (tnb_body3) for this problem?  SRHIP_TN_T3=0: one tap per block
-bool tnb_t3_shape(int conv, int NI, int NJ, int w) {
-  static const int on = [] { const char* e = sr_getenv("SRHIP_TN_T3"); return !(e && e[0] == '0'); }();
-  return on && conv && w == 1 && NI % 64 == 0 && NJ % 64 == 0;
-}
-bool tnb_t3_ok(const TnArgs& p, int w) {
-  return tnb_t3_shape(p.conv, p.NI, p.NJ, w) && !p.a_rowscale && p.b_mode == 0;
-}
-constexpr int lds_bytes3() { return 2 * 3 * 4 * 64 * 32; }
-// all nine taps per block (tnb_body9: two fp16 planes only)?  SRHIP_TN_T9=0 (experiments build): the three-tap form
-bool tnb_t9_shape(int conv, int NI, int NJ, int w) {
-#ifdef SR_TN_T9_OFF
-  return false;                                    // build variant for the same-box A/B (make EXTRA=-DSR_TN_T9_OFF)
-#endif
-  static const int on = [] { const char* e = sr_getenv("SRHIP_TN_T9"); return !(e && e[0] == '0'); }();
-  static const int f16 = [] { const char* e = sr_getenv("SRHIP_TN_F16X2"); return !(e && e[0] == '0'); }();
-  return on && f16 && tnb_t3_shape(conv, NI, NJ, w);
-}
-bool tnb_t9_ok(const TnArgs& p, int w) { return tnb_t9_shape(p.conv, p.NI, p.NJ, w) && tnb_t3_ok(p, w); }
-// two fp16 planes / three products in the three-tap kernels (default); SRHIP_TN_F16X2=0: three bf16 planes / six products
-bool tnb_f16() {
-  static const int on = [] { const char* e = sr_getenv("SRHIP_TN_F16X2"); return !(e && e[0] == '0'); }();
-  return on;
-}
-
 int pick_tile(int n, int* w) {
   if (n % 180 == 0) { *w = 3; return 180; }
   if (n <= 64) { *w = 1; return 64; }
@@ -1920,26 +1588,60 @@ int pick_w(int NI, int NJ, int* tile) {
   return w;
 }
 
-// The strip form of the nine-tap block (tnb_body9s): image width a multiple of 64, at least one slice per strip, four rows per
-// slice.  Channel counts: every conv of at least 64 channels on either side, in 64-column tiles -- the last one partly empty
-// where a count is no multiple of 64.  Against the one-tap-per-block kernels of the wider tiles (launch + reducer, 8 x 64 x 64,
-// same box): 180 -> 180 114 -> 90 us, 180 -> 64 107 -> 66, 128 -> 128 85 -> 60 (8 x 128 x 128: 262 -> 142), 256 -> 256
-// 247 -> 137, 192 -> 192 107 -> 90, 96 -> 96 75 -> 57.  SRHIP_TN_T9S=0 / SRHIP_TN_T9S_RAGGED=0 (experiments build): off /
-// multiples of 64 only.
-bool tnb_t9s_shape(int conv, int NI, int NJ) {
+// The kernel form of a weight-gradient problem: tnb_form() below is the one place that chooses it.
+enum TnbForm {
+  TNB_PLAIN,    // k_tnb<W> / k_tnb_conv_batched<W>: one tap per block, three bf16 planes / six products
+  TNB_HC,       // k_tnb_hc<W> (single conv problems; the batched launch runs k_tnb_conv_batched<W>): 128- / 192-column tiles,
+                // two fp16 planes / three products.  (64-column tiles stay on k_tnb<1>: SwinIR's 180 -> 64 conv 78 us there,
+                // 97 us on this body -- the per-lane row offsets weigh more where a lane stages one column.)
+  TNB_NINE,     // k_tnb9 / k_tnb9_conv_batched: all nine taps per block in token order, 64 x 64 tiles
+  TNB_STRIP9,   // k_tnb9s / k_tnb9s_conv_batched: all nine taps per block, strip walk, 64-column tiles
+};
+
+// The strip form (tnb_body9s) takes every conv of at least 64 channels on either side, in 64-column tiles -- the last one
+// partly empty where a count is no multiple of 64.  Against the one-tap-per-block kernels of the wider tiles (launch +
+// reducer, 8 x 64 x 64, same box): 180 -> 180 114 -> 90 us, 180 -> 64 107 -> 66, 128 -> 128 85 -> 60 (8 x 128 x 128:
+// 262 -> 142), 256 -> 256 247 -> 137, 192 -> 192 107 -> 90, 96 -> 96 75 -> 57.  Experiments build: SRHIP_TN_T9S=0 off
+// (the 64 x 64 tiles of TNB_NINE shapes go to k_tnb9), SRHIP_TN_T9S_RAGGED=0 TNB_NINE shapes only;
+// SRHIP_TN_F16X2_CONV3=0: no TNB_HC.
+//
+// Without p (the planners): what the channel counts allow.  The plan's slice count is the strip form's also where the image
+// geometry later sends the launch to k_tnb9 or one tap per block.  With p (the launchers): plain operands (no row scale, no
+// prologue) for every fp16 form; the strip form needs an image width a multiple of 64, at least one slice per strip, four
+// rows per slice and, with the PixelShuffle gradient, a Cout of whole 64-column tiles; k_tnb_hc neither the PixelShuffle
+// form nor operands of 4 GB and more (32-bit row offsets).
+TnbForm tnb_form(int conv, int NI, int NJ, const TnArgs* p = nullptr) {
 #ifdef SR_TN_T9S_OFF
-  return false;                                    // build variant for the same-box A/B (make EXTRA=-DSR_TN_T9S_OFF)
+  constexpr int strip = 0;                          // build variant for the same-box A/B (make EXTRA=-DSR_TN_T9S_OFF)
+#else
+  static const int strip = [] { const char* e = sr_getenv("SRHIP_TN_T9S"); return !(e && e[0] == '0'); }();
 #endif
-  static const int on = [] { const char* e = sr_getenv("SRHIP_TN_T9S"); return !(e && e[0] == '0'); }();
   static const int ragged = [] { const char* e = sr_getenv("SRHIP_TN_T9S_RAGGED"); return e ? atoi(e) : 1; }();
-  if (!on || !tnb_f16() || !conv) return false;
-  int t;
-  if (tnb_t9_shape(conv, NI, NJ, pick_w(NI, NJ, &t))) return true;
-  return ragged && NI >= 64 && NJ >= 64;
+  static const int f16c3 = [] { const char* e = sr_getenv("SRHIP_TN_F16X2_CONV3"); return e ? atoi(e) : 1; }();
+  if (!conv || (p && (p->a_rowscale || p->b_mode != 0))) return TNB_PLAIN;
+  int tile;
+  const int w = pick_w(NI, NJ, &tile);
+  const bool nine = w == 1 && NI % 64 == 0 && NJ % 64 == 0;
+  if (strip && (nine || (ragged && NI >= 64 && NJ >= 64)) &&
+      (!p || (p->Wd % 64 == 0 && p->S >= p->Wd / 64 && (!p->ps || NI % 64 == 0) &&
+              (long)p->batch * p->H * (p->Wd / 64) >= 4L * p->S)))   // (fewer rows: more halo rows staged than rows)
+    return TNB_STRIP9;
+  if (nine) return TNB_NINE;
+  if (w >= 2 && f16c3 &&
+      (!p || (!p->ps && (long)p->M * p->lda < (1L << 30) && (long)p->batch * p->H * p->Wd * p->ldb < (1L << 30))))
+    return TNB_HC;
+  return TNB_PLAIN;
 }
-bool tnb_t9s_ok(const TnArgs& p) {
-  return tnb_t9s_shape(p.conv, p.NI, p.NJ) && !p.a_rowscale && p.b_mode == 0 && p.Wd % 64 == 0 && p.S >= p.Wd / 64 &&
-         (long)p.batch * p.H * (p.Wd / 64) >= 4L * p.S;      // a slice of fewer than four rows stages more halo rows than rows
+TnbForm tnb_form(const TnArgs& p) { return tnb_form(p.conv, p.NI, p.NJ, &p); }
+
+// the planners' view: blocks per slice of a problem's launch; *nine: all nine taps per block (TNB_NINE / TNB_STRIP9)
+long tnb_plan_blocks(int conv, int NI, int NJ, int* w, bool* nine) {
+  int tile;
+  *w = pick_w(NI, NJ, &tile);
+  const TnbForm f = tnb_form(conv, NI, NJ);
+  *nine = f == TNB_NINE || f == TNB_STRIP9;
+  if (f == TNB_STRIP9) tile = 64;
+  return (long)sr_cdiv(NI, tile) * sr_cdiv(NJ, tile) * (conv && !*nine ? 9 : 1);
 }
 
 template <typename K>
@@ -1950,6 +1652,8 @@ int reserve_lds(K kern, int bytes, const char* name) {
 }
 
 constexpr int lds_bytes(int w) { return 2 * 3 * 2 * 64 * w * 64; }
+// blocks of k_tnb<1> / k_tnb_conv_batched<1> in flight: three 8-wave blocks per CU (lds_bytes(1) = 49 KB each) on 256 CUs
+constexpr long TNB_W1_SLOTS = 3 * 256;
 
 }  // namespace
 
@@ -1991,32 +1695,15 @@ int sr_gemm_tnb_grouped(TnArgs* probs, int n, hipStream_t st) {
     }                                                                                     \
     hipLaunchKernelGGL((k_tnb_grouped<W_>), grid, dim3(512), lds_bytes(W_), st, g);       \
   }
-#ifdef SRHIP_EXPERIMENTS
-  const char* dbg_env = sr_getenv("SRHIP_TN_DBG");
-  const int dbg = dbg_env ? atoi(dbg_env) : 0;      // role ablations (results are wrong on purpose)
-#else
-  constexpr int dbg = 0;
-#endif
-  // 192-column tiles on two fp16 planes / three products (tnb_body_h); SRHIP_TN_F16X2_LINEAR=0: bf16x3 / six
-  static const int f16lin = [] { const char* e = sr_getenv("SRHIP_TN_F16X2_LINEAR"); return e ? atoi(e) : 1; }();
-  if (w == 3 && !dbg && f16lin) {
+  if (w == 3) {            // 192-column tiles on two fp16 planes / three products (tnb_body_h)
     static bool attr_h = false;
     if (!attr_h) {
       if (int rc = reserve_lds(k_tnb_grouped_h<3>, lds_bytes(3), "k_tnb_grouped_h")) return rc;
       attr_h = true;
     }
     hipLaunchKernelGGL((k_tnb_grouped_h<3>), grid, dim3(512), lds_bytes(3), st, g);
-  } else
-#ifdef SRHIP_EXPERIMENTS
-  if (w == 3 && dbg == 1) { hipLaunchKernelGGL((k_tnb_grouped<3, 1>), grid, dim3(512), lds_bytes(3), st, g); }
-  else if (w == 3 && dbg == 2) { hipLaunchKernelGGL((k_tnb_grouped<3, 2>), grid, dim3(512), lds_bytes(3), st, g); }
-  else if (w == 3 && dbg == 4) { hipLaunchKernelGGL((k_tnb_grouped<3, 4>), grid, dim3(512), lds_bytes(3), st, g); }
-  else if (w == 3 && dbg == 3) { hipLaunchKernelGGL((k_tnb_grouped<3, 3>), grid, dim3(512), lds_bytes(3), st, g); }
-  else
-#endif
-  {
-  SR_TNB_G(1) SR_TNB_G(2) SR_TNB_G(3)
   }
+  SR_TNB_G(1) SR_TNB_G(2)
 #undef SR_TNB_G
   SR_LAUNCH_CHECK("k_tnb_grouped");
   return 0;
@@ -2037,7 +1724,8 @@ int sr_gemm_tnb(TnArgs& p, hipStream_t st) {
   dim3 grid(p.S, tiles, 1);
   if (p.conv) grid = dim3(p.S * tiles * 9, 1, 1);
   static const int xcd = [] { const char* e = sr_getenv("SRHIP_TN_XCD"); return !(e && e[0] == '0'); }();
-  if (tnb_t9s_ok(p) && (!p.ps || p.NI % 64 == 0)) {      // nine taps per block, strip walk, 64-column tiles
+  const TnbForm form = tnb_form(p);
+  if (form == TNB_STRIP9) {
     p.i_tile = p.j_tile = 64;
     tiles = sr_cdiv(p.NI, 64) * sr_cdiv(p.NJ, 64);
     p.aux = p.part + (long)p.S * 9 * p.NI * p.NJ;          // (sr_tn_plan_bx3 sized the workspace for it)
@@ -2061,7 +1749,7 @@ int sr_gemm_tnb(TnArgs& p, hipStream_t st) {
     SR_LAUNCH_CHECK("k_tnb9s");
     return 0;
   }
-  if (tnb_t9_ok(p, w)) {       // 64-wide conv problem: all nine taps per block, one block per CU
+  if (form == TNB_NINE) {
     static bool attr9 = false;
     if (!attr9) {
       if (int rc = reserve_lds(k_tnb9<0>, T9_LDS, "k_tnb9")) return rc;
@@ -2080,33 +1768,7 @@ int sr_gemm_tnb(TnArgs& p, hipStream_t st) {
     SR_LAUNCH_CHECK("k_tnb9");
     return 0;
   }
-  if (tnb_t3_ok(p, w)) {       // 64-wide conv problem: three taps per block
-    static bool attr3 = false;
-    if (!attr3) {
-      if (int rc = reserve_lds(k_tnb3<0>, lds_bytes3(), "k_tnb3")) return rc;
-      attr3 = true;
-    }
-#ifdef SRHIP_EXPERIMENTS
-    {   // role ablations (wrong results on purpose; tools/mb_tnb3.py): 1 = consumers skip their MFMAs, 2 = producers neither load nor store
-      const char* e = sr_getenv("SRHIP_TN_DBG");
-      const int dbg = e ? atoi(e) : 0;
-      if (dbg == 1 && tnb_f16()) { hipLaunchKernelGGL((k_tnb3<1, true>), dim3(p.S * tiles * 3), dim3(512), lds_bytes3(), st, p, tiles, xcd); return 0; }
-      if (dbg == 2 && tnb_f16()) { hipLaunchKernelGGL((k_tnb3<2, true>), dim3(p.S * tiles * 3), dim3(512), lds_bytes3(), st, p, tiles, xcd); return 0; }
-      if (dbg == 5 && tnb_f16()) { hipLaunchKernelGGL((k_tnb3<5, true>), dim3(p.S * tiles * 3), dim3(512), lds_bytes3(), st, p, tiles, xcd); return 0; }
-    }
-#endif
-    if (tnb_f16()) hipLaunchKernelGGL((k_tnb3<0, true>), dim3(p.S * tiles * 3), dim3(512), lds_bytes3(), st, p, tiles, xcd);
-    else hipLaunchKernelGGL((k_tnb3<0>), dim3(p.S * tiles * 3), dim3(512), lds_bytes3(), st, p, tiles, xcd);
-    SR_LAUNCH_CHECK("k_tnb3");
-    return 0;
-  }
-  // single conv problems with plain operands on 128- and 192-column tiles: two fp16
-  // planes / three products (k_tnb_hc); SRHIP_TN_F16X2_CONV3=0: six bf16
-  static const int f16c3 = [] { const char* e = sr_getenv("SRHIP_TN_F16X2_CONV3"); return e ? atoi(e) : 1; }();
-  // (64-column tiles stay on k_tnb<1>: SwinIR's 180 -> 64 conv 78 us there, 97 us on this body -- the per-lane row offsets
-  // weigh more where a lane stages one column)
-  if (p.conv && w >= 2 && f16c3 && tnb_f16() && !p.ps && p.b_mode == 0 && !p.a_rowscale &&
-      (long)p.M * p.lda < (1L << 30) && (long)p.batch * p.H * p.Wd * p.ldb < (1L << 30)) {
+  if (form == TNB_HC) {
     static bool attr_hc[4] = {false, false, false, false};
 #define SR_TNB_HC(W_)                                                                       \
     if (w == W_) {                                                                          \
@@ -2137,18 +1799,14 @@ int sr_gemm_tnb(TnArgs& p, hipStream_t st) {
 }
 
 int sr_conv_wgrad_batched_plan(int n, int M, int NI, int NJ, int* S, long* part_floats_per_item) {
-  int tile;
-  const int w = pick_w(NI, NJ, &tile);
-  const bool t3 = tnb_t3_shape(1, NI, NJ, w);             // three taps per block
-  const bool t9s = tnb_t9s_shape(1, NI, NJ);
-  const bool t9 = t9s || tnb_t9_shape(1, NI, NJ, w);      // nine: one block per (tile, slice), one block per CU
-  if (t9s) tile = 64;
-  const long tiles = (long)sr_cdiv(NI, tile) * sr_cdiv(NJ, tile) * (t9 ? 1 : (t3 ? 3 : 9)) * n;
+  int w;
+  bool t9;
+  const long tiles = tnb_plan_blocks(1, NI, NJ, &w, &t9) * n;
   // Blocks in flight: 3 per CU for 64-wide tiles (49 KB of LDS each), else 1.  The slice count is chosen
   // for WHOLE rounds of blocks -- 33 problems x 9 taps x 3 slices = 891 blocks on 768 slots ran 1.16
   // rounds, i.e. the second round 16 % full (x4: 5.3 ms for what 1.93 rounds do in 3.1) -- among the
   // counts that leave a slice at least 1024 rows; ties go to fewer slices (less partial traffic).
-  const long slots = t9 ? 256 : (w == 1 ? 128L * SR_TNB3_OCC : 256);
+  const long slots = w == 1 && !t9 ? TNB_W1_SLOTS : 256;
   long best = 1;
   double best_eff = 0.0;
   for (long s = 1; s <= 64; ++s) {
@@ -2183,7 +1841,8 @@ int sr_conv_wgrad_batched_tnb(const TnArgs& base, const float* const* A, const f
   for (int k = 0; k < n; ++k) { g.A[k] = A[k]; g.B[k] = B[k]; }
   static const int xcd = [] { const char* e = sr_getenv("SRHIP_TN_XCD"); return !(e && e[0] == '0'); }();
   g.xcd = xcd;
-  if (tnb_t9s_ok(g.base)) {    // all nine taps per block, strip walk
+  const TnbForm form = tnb_form(g.base);      // (no batched k_tnb_hc: TNB_HC runs k_tnb_conv_batched)
+  if (form == TNB_STRIP9) {
     g.base.i_tile = g.base.j_tile = 64;
     g.tiles = sr_cdiv(base.NI, 64) * sr_cdiv(base.NJ, 64);
     g.base.aux = base.part + (long)n * part_stride;        // behind the n problems' partial sums (the plan sized it)
@@ -2198,7 +1857,7 @@ int sr_conv_wgrad_batched_tnb(const TnArgs& base, const float* const* A, const f
     SR_LAUNCH_CHECK("k_tnb9s_conv_batched");
     return 0;
   }
-  if (tnb_t9_ok(g.base, w)) {  // all nine taps per block
+  if (form == TNB_NINE) {
     static bool attr9 = false;
     if (!attr9) {
       if (int rc = reserve_lds(k_tnb9_conv_batched, T9_LDS, "k_tnb9_conv_batched")) return rc;
@@ -2206,17 +1865,6 @@ int sr_conv_wgrad_batched_tnb(const TnArgs& base, const float* const* A, const f
     }
     hipLaunchKernelGGL(k_tnb9_conv_batched, dim3(base.S * g.tiles * n), dim3(T9_THREADS), T9_LDS, st, g);
     SR_LAUNCH_CHECK("k_tnb9_conv_batched");
-    return 0;
-  }
-  if (tnb_t3_ok(g.base, w)) {  // three taps per block
-    static bool attr3 = false;
-    if (!attr3) {
-      if (int rc = reserve_lds(k_tnb3_conv_batched<0>, lds_bytes3(), "k_tnb3_conv_batched")) return rc;
-      attr3 = true;
-    }
-    if (tnb_f16()) hipLaunchKernelGGL((k_tnb3_conv_batched<0, true>), dim3(base.S * 3 * g.tiles * n), dim3(512), lds_bytes3(), st, g);
-    else hipLaunchKernelGGL((k_tnb3_conv_batched<0>), dim3(base.S * 3 * g.tiles * n), dim3(512), lds_bytes3(), st, g);
-    SR_LAUNCH_CHECK("k_tnb3_conv_batched");
     return 0;
   }
   dim3 grid(base.S * 9 * g.tiles * n, 1, 1);
@@ -2239,16 +1887,11 @@ int sr_conv_wgrad_batched_tnb(const TnArgs& base, const float* const* A, const f
 // (98 / 147 KB of LDS each), THREE per CU for 64-wide tiles (49 KB) -- at 64 channels the launch was
 // short of blocks with the per-CU budget of the wide tiles (28 slices x 9 taps: 212 us; 85 x 9: 147 us).
 int sr_tn_plan_bx3(int M, int NI, int NJ, int conv, int* S, long* part_floats) {
-  int tile;
-  const int w = pick_w(NI, NJ, &tile);
-  const bool t3 = tnb_t3_shape(conv, NI, NJ, w);          // three taps per block
-  const bool t9s = tnb_t9s_shape(conv, NI, NJ);           // nine taps per block in 64-column tiles, one block per CU
-  const bool t9 = t9s || tnb_t9_shape(conv, NI, NJ, w);   // (the slice count of a shape is the strip form's also where an image
-  if (t9s) tile = 64;                                     //  width sends the call to another kernel: the plan does not see it)
-  const long tiles = (long)sr_cdiv(NI, tile) * sr_cdiv(NJ, tile) * (conv ? (t9 ? 1 : (t3 ? 3 : 9)) : 1);
-  static const long t1 = [] { const char* e = sr_getenv("SRHIP_TNB_BLOCKS_W1"); return e ? atol(e) : 768L; }();
-  static const long t3b = [] { const char* e = sr_getenv("SRHIP_TNB_BLOCKS_T3"); return e ? atol(e) : 768L; }();
-  long s = (t9 ? 256 : (t3 ? t3b : (w == 1 ? t1 : 256))) / tiles;
+  int w;
+  bool t9;
+  const long tiles = tnb_plan_blocks(conv, NI, NJ, &w, &t9);
+  static const long t1 = [] { const char* e = sr_getenv("SRHIP_TNB_BLOCKS_W1"); return e ? atol(e) : TNB_W1_SLOTS; }();
+  long s = (w == 1 && !t9 ? t1 : 256) / tiles;
   const long smax = (M + 127) / 128;
   if (s > smax) s = smax;
   if (s > 256) s = 256;

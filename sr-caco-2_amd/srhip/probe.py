@@ -5,7 +5,7 @@ the timed region.  Off by default (zero overhead beyond one attribute check).
 Op classes ("kinds") and the kernels behind them:
   gemm_nt     Linear forward / data gradient            k_nth2 / k_ntw (gemm_ntw.hip; fp16x2 / bf16x3 planes), k_nt* exact f32
   conv_nt     3x3 conv forward / data gradient          k_nhcw / k_nhcw2<..> implicit GEMM (gemm_ntw.hip), k_ntb (gemm_ntb.hip)
-  conv_tn     3x3 conv weight gradient                  k_tnb<W> / k_tnb3 conv forms (gemm_tnb.hip)
+  conv_tn     3x3 conv weight gradient                  k_tnb9s / k_tnb9 / k_tnb_hc<W> / k_tnb<W> (gemm_tnb.hip)
   linear_tn   Linear weight gradients (grouped launch)  k_tnb_grouped_h<W> (gemm_tnb.hip)
   wattn       window attention core, backward           k_wattn3_bwd (wattn2.hip); exact f32: k_wattn_* (wattn.hip)
   wmsa_fused  norm1 + qkv + attention + proj, forward   k_wmsa_f16h (wmsa_f16.hip)

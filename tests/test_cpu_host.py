@@ -58,13 +58,74 @@ def test_ctypes_structs_mirror_the_header(tmp_path):
         assert getattr(cls, last).offset == int(off), (name, last)
 
 
+# (S, part_floats) of the bx3 planners, recorded before the weight-gradient kernel forms were chosen in one place:
+# srhip_tn_plan_bx3 (M, NI, NJ, conv) at SwinIR's Linears and 180 -> 180 conv, EDSR's 64 -> 64 and 64 -> 256 (PixelShuffle)
+# convs at 8 x 64^2 / 128^2 / 256^2, DRRN's 128 -> 128 and ragged / narrow widths; srhip_conv3x3_wgrad_batched_plan
+# (n, B, H, W, Cout, Cin)
+TN_PLAN_BX3 = {
+    (32768, 180, 180, 0): (256, 8294400),
+    (32768, 180, 180, 1): (28, 8245440),
+    (32768, 540, 180, 0): (85, 8262000),
+    (32768, 540, 180, 1): (9, 7950960),
+    (32768, 360, 180, 0): (128, 8294400),
+    (32768, 360, 180, 1): (14, 8245440),
+    (32768, 180, 360, 0): (128, 8294400),
+    (32768, 180, 360, 1): (14, 8245440),
+    (32768, 64, 64, 0): (256, 1048576),
+    (32768, 64, 64, 1): (256, 9519104),
+    (131072, 64, 64, 0): (256, 1048576),
+    (131072, 64, 64, 1): (256, 9519104),
+    (524288, 64, 64, 0): (256, 1048576),
+    (524288, 64, 64, 1): (256, 9519104),
+    (32768, 256, 64, 0): (192, 3145728),
+    (32768, 256, 64, 1): (64, 9519104),
+    (131072, 256, 64, 0): (192, 3145728),
+    (131072, 256, 64, 1): (64, 9519104),
+    (524288, 256, 64, 0): (192, 3145728),
+    (524288, 256, 64, 1): (64, 9519104),
+    (32768, 128, 128, 0): (256, 4194304),
+    (32768, 128, 128, 1): (64, 9519104),
+    (2097152, 128, 128, 0): (256, 4194304),
+    (2097152, 128, 128, 1): (64, 9519104),
+    (4096, 96, 96, 0): (32, 294912),
+    (4096, 96, 96, 1): (32, 2695168),
+    (4096, 184, 184, 0): (32, 1083392),
+    (4096, 184, 184, 1): (28, 8612352),
+    (4096, 200, 200, 0): (32, 1280000),
+    (4096, 200, 200, 1): (16, 5841920),
+    (4096, 64, 96, 0): (32, 196608),
+    (4096, 64, 96, 1): (32, 1789952),
+    (4096, 96, 64, 0): (32, 196608),
+    (4096, 96, 64, 1): (32, 1789952),
+}
+CONV_WGRAD_BATCHED_PLAN = {
+    (33, 8, 64, 64, 64, 64): (23, 855232),
+    (33, 8, 128, 128, 64, 64): (23, 855232),
+    (33, 8, 256, 256, 64, 64): (23, 855232),
+    (1, 8, 64, 64, 180, 180): (28, 8245440),
+    (2, 8, 64, 64, 256, 64): (32, 4759552),
+    (4, 8, 64, 64, 128, 128): (16, 2379776),
+    (5, 2, 24, 40, 96, 96): (1, 84224),
+    (3, 1, 9, 7, 184, 184): (1, 307584),
+    (3, 2, 16, 16, 200, 200): (1, 365120),
+    (7, 2, 16, 16, 64, 96): (1, 55936),
+}
+
+
 def test_plan_queries_need_no_gpu():
+    import ctypes
     from srhip import ops
     S, n = ops.tn_plan(32768, 180, 180)
     assert S >= 1 and n == S * 180 * 180
     S9, n9 = ops.tn_plan(32768, 180, 180, conv=True)
     # the nine taps' partial sums + the strip-form kernel's per-block words (320 floats for each of the 3 x 3 64-column tiles)
     assert n9 == S9 * 9 * 180 * 180 + S9 * 9 * 320
+    for (M, NI, NJ, conv), want in TN_PLAN_BX3.items():
+        assert ops.tn_plan(M, NI, NJ, conv=bool(conv), bx=True) == want, (M, NI, NJ, conv)
+    for (k, B, H, W, Co, Ci), want in CONV_WGRAD_BATCHED_PLAN.items():
+        S, per = ctypes.c_int(0), ctypes.c_long(0)
+        ops.call("srhip_conv3x3_wgrad_batched_plan", k, B, H, W, Co, Ci, ctypes.addressof(S), ctypes.addressof(per))
+        assert (S.value, per.value) == want, (k, B, H, W, Co, Ci)
 
 
 def test_cpu_tensors_fail_loudly():

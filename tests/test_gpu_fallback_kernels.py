@@ -17,8 +17,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # sr-caco-2_amd/lib/libsrhip_exp.so, built by __graft_entry__.build()); the shipped library ignores them.  An arm that sets
 # one runs on that build (SRHIP_LIB) and its child asserts that the build really reads them; Python-side switches
 # (srhip/ops.py, the engines) work with either library.
-C_SIDE = {"SRHIP_NTW", "SRHIP_NTW_GRID", "SRHIP_NTW_ROT", "SRHIP_TN_F16X2", "SRHIP_TN_F16X2_LINEAR", "SRHIP_TN_GROUP_XCD",
-          "SRHIP_TN_T3", "SRHIP_TN_XCD", "SRHIP_WA_XCD", "SRHIP_TN_BLOCKS", "SRHIP_WMSA_NW"}
+C_SIDE = {"SRHIP_NTW", "SRHIP_NTW_GRID", "SRHIP_NTW_ROT", "SRHIP_TN_GROUP_XCD", "SRHIP_TN_XCD", "SRHIP_WA_XCD",
+          "SRHIP_TN_BLOCKS", "SRHIP_WMSA_NW"}
 EXP_LIB = os.path.join(ROOT, "sr-caco-2_amd", "lib", "libsrhip_exp.so")
 ASSERT_EXP = "from srhip import ops as _o\nassert _o.lib.srhip_experiments_enabled() == 1, 'the loaded library ignores C-side switches'\n"
 
@@ -255,14 +255,15 @@ TN16_CHILD = textwrap.dedent('''
 ''')
 
 
-@pytest.mark.parametrize("env", [{}, {"SRHIP_TN_F16X2": "0", "SRHIP_TN_F16X2_LINEAR": "0", "SRHIP_TN_GROUP_XCD": "0"}])
+@pytest.mark.parametrize("env", [{}, {"SRHIP_TN_XCD": "0", "SRHIP_TN_GROUP_XCD": "0"}])
 def test_fp16x2_three_product_conv_weight_gradient_is_f32_grade(env):
-    """The three-tap conv weight-gradient kernels (k_tnb3 / k_tnb3_conv_batched) with two fp16 planes, one running
-    power-of-two scale per operand COLUMN (channel) and three products: every row of dW, relative to its largest entry,
-    is within 3x of an f32 autograd -- on gradient-like inputs (pixels and channels decades apart), on magnitudes that
-    rise by 2^40 along the tokens (the scales must follow and the sums be rescaled) and with all-zero channels;
-    the same for the grouped Linear weight gradients (tnb_body_h: DropPath row scale, LayerNorm and GELU prologues).
-    Second arm: the bf16x3 / six-product forms and the old block order."""
+    """The 64-wide conv weight gradient with all nine taps per block (k_tnb9; k_tnb9s where the image width is a multiple
+    of 64 and the slices hold four rows) on two fp16 planes, one running power-of-two scale per operand COLUMN (channel) and
+    three products: every row of dW, relative to its largest entry, is within 3x of an f32 autograd -- on gradient-like
+    inputs (pixels and channels decades apart), on magnitudes that rise by 2^40 along the tokens (the scales must follow
+    and the sums be rescaled) and with all-zero channels; the same for the grouped Linear weight gradients
+    (k_tnb_grouped_h, tnb_body_h: DropPath row scale, LayerNorm and GELU prologues).  Second arm (experiments build): the
+    block orders that ignore the XCDs."""
     cenv, pre = child_env(env)
     r = subprocess.run([sys.executable, "-c", pre + TN16_CHILD], cwd=ROOT, env=cenv,
                        capture_output=True, text=True, timeout=600)

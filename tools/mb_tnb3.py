@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""Microbenchmark of the 64-wide conv weight-gradient kernel (k_tnb3: three taps per block) at EDSR x8's shapes, with the role
-ablations of the experiments build (SRHIP_LIB=.../libsrhip_exp.so, SRHIP_TN_DBG=0|1|2: all | no MFMAs | no staging).
+"""Microbenchmark of the 64-wide conv weight gradient at EDSR x8's shapes -- written for the three-tap kernel (since removed);
+those shapes now run nine taps per block (k_tnb9 at 8 x 64 x 64, the strip form k_tnb9s for the PixelShuffle upsampler
+convs) -- with the role ablations of the experiments build (SRHIP_LIB=.../libsrhip_exp.so, SRHIP_TN_DBG=0|1|2: all | no
+MFMAs | no staging).
 usage (GPU box, repo root): SRHIP_LIB=$PWD/sr-caco-2_amd/lib/libsrhip_exp.so python tools/mb_tnb3.py"""
 import os
 import subprocess
