@@ -466,6 +466,19 @@ int srhip_resize_cubic(const void* src, void* dst, int is_u8, int B, int H, int 
 int srhip_u8_to_unit(const unsigned char* src, float* dst, long n, void* stream);
 int srhip_clip01(float* x, long n, void* stream);
 
+/* ---- the target pyramid of the multi-scale training losses, one launch (resize.hip) ------------------------------ */
+/* loss_prosr / loss_mslaprs (dlib/models/model_plain.py:257-264,298-305): every intermediate image is compared with
+ * torch.clamp(F.interpolate(H, size = its size, mode = 'bicubic', align_corners = True), 0, 1).  src: B images [H][W],
+ * float32; levels[i].dst: B images [Ho][Wo], i < n <= 8, all written by ONE launch.  torch's bicubic: A = -0.75, source
+ * coordinate o * (H - 1) / (Ho - 1) (0 when Ho == 1), border indices clamped, no antialiasing; clamp01 != 0 clamps to
+ * [0, 1] (a NaN stays a NaN).  The coordinate is the exact rational, coefficients and sums are f64 and the result is
+ * rounded once: torch's float64 result to half an f32 ulp (its float32 kernel, whose coordinate is an f32 product, sits
+ * up to 6e-5 from that at 512 pixels).  No level may overlap the source or another level; a level whose rows are
+ * multiples of 4 pixels and whose dst is 16-byte aligned is stored as float4.  Bit-identical from run to run. */
+typedef struct { float* dst; int Ho, Wo; } srhip_pyr_level;
+int srhip_resize_bicubic_ac_pyramid(const float* src, int B, int H, int W, const srhip_pyr_level* levels, int n,
+                                    int clamp01, void* stream);
+
 /* ---- helpers of the generic conv-net engine (tape_ops.hip; DBPN / SRFBN / ProSR: SURVEY f1) ---------------- */
 /* nn.PReLU(num_parameters = 1) (dlib/models/network_dbpn.py:85-86, network_srfbn.py:38-46): y = x > 0 ? x : a x with
  * the slope read from device memory; backward dx = g (x > 0 ? 1 : a) (dx may alias g) and dalpha (+)= sum g min(x, 0)

@@ -83,6 +83,95 @@ __global__ void __launch_bounds__(256) k_clip01(float* __restrict__ x, long n) {
   for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) x[i] = fminf(fmaxf(x[i], 0.f), 1.f);
 }
 
+// ---- the multi-scale loss's target pyramid: F.interpolate(mode="bicubic", align_corners=True) [+ clamp to [0, 1]] ----------
+// torch's bicubic (aten/src/ATen/native/UpSample.h: area_pixel_compute_scale / guard_index_and_lambda /
+// get_cubic_upsample_coefficients, A = -0.75; cpu/UpSampleKernel.cpp: separable, horizontal inside vertical), evaluated the
+// way torch evaluates it on float64 input and rounded ONCE to f32.  torch's float32 kernel forms the source coordinate as the
+// f32 product of an f32 scale (H - 1) / (Ho - 1) and the output index: at 512 pixels that moves the fractional part by ~3e-5
+// and the resized target by up to 6e-5 (3e-6 at 32 pixels) -- 2.5e-5 of the L2 gradient 2 lam (y - t) / N of a level whose
+// output sits 0.1 from the target, where the loss kernels themselves are held to 1e-6.  Here the coordinate is the exact
+// rational o (H - 1) / (Ho - 1) (integer quotient and remainder), the four coefficients and the 16-tap sum are f64 (the
+// f64 FMA rate of this GPU equals the f32 one; the kernel waits for its 16 loads per pixel either way).
+constexpr int PYR_MAXL = 8;     // levels per launch
+constexpr int PYR_RUN = 4;      // consecutive output pixels of one row per thread: one 16-byte store
+constexpr int PYR_MAXDIM = 32768;   // image edge: o * (n_in - 1) stays inside 32 bits
+
+struct PyrArgs {
+  float* dst[PYR_MAXL];
+  int Ho[PYR_MAXL], Wo[PYR_MAXL];
+  int runs[PYR_MAXL];           // runs per output row: ceil(Wo / PYR_RUN)
+  int vec[PYR_MAXL];            // rows are whole runs and dst is 16-byte aligned: float4 stores
+  int blk0[PYR_MAXL + 1];       // first block of each level (prefix sums): block -> level
+  int n;
+};
+
+__device__ __forceinline__ void bicubic_coeffs_torch(double t, double (&c)[4]) {
+  const double A = -0.75;
+  const double x0 = t + 1.0, x2 = 1.0 - t, x3 = x2 + 1.0;
+  c[0] = ((A * x0 - 5.0 * A) * x0 + 8.0 * A) * x0 - 4.0 * A;
+  c[1] = ((A + 2.0) * t - (A + 3.0)) * t * t + 1.0;
+  c[2] = ((A + 2.0) * x2 - (A + 3.0)) * x2 * x2 + 1.0;
+  c[3] = ((A * x3 - 5.0 * A) * x3 + 8.0 * A) * x3 - 4.0 * A;
+}
+
+// source index and fractional part of output index o < n_out: o * (n_in - 1) / (n_out - 1), 0 for a single output pixel
+__device__ __forceinline__ int bicubic_src(int n_in, int n_out, int o, double& t) {
+  if (n_out == 1) { t = 0.0; return 0; }
+  const unsigned num = (unsigned)o * (unsigned)(n_in - 1), d = (unsigned)(n_out - 1);   // sizes <= PYR_MAXDIM: no overflow
+  const unsigned q = num / d;
+  t = (double)(num - q * d) / (double)d;
+  return (int)q;
+}
+
+__global__ void __launch_bounds__(256) k_bicubic_ac_pyramid(const float* __restrict__ src, int B, int H, int W, PyrArgs a,
+                                                            int clamp01) {
+  int l = 0;
+  while (l + 1 < a.n && (int)blockIdx.x >= a.blk0[l + 1]) ++l;
+  const int Ho = a.Ho[l], Wo = a.Wo[l], runs = a.runs[l];
+  const long item = (long)((int)blockIdx.x - a.blk0[l]) * 256 + threadIdx.x;
+  if (item >= (long)B * Ho * runs) return;
+  const int ox0 = (int)(item % runs) * PYR_RUN;
+  const long row = item / runs;                 // b * Ho + oy
+  const int oy = (int)(row % Ho);
+  const float* img = src + (row / Ho) * (long)H * W;
+  double ty, cy[4];
+  const int iy = bicubic_src(H, Ho, oy, ty);
+  bicubic_coeffs_torch(ty, cy);
+  const float* r[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) r[k] = img + (long)min(max(iy - 1 + k, 0), H - 1) * W;
+  float out[PYR_RUN];
+#pragma unroll
+  for (int j = 0; j < PYR_RUN; ++j) {
+    const int ox = min(ox0 + j, Wo - 1);        // a ragged row's last run recomputes its last pixel; stored once below
+    double tx, cx[4];
+    const int ix = bicubic_src(W, Wo, ox, tx);
+    bicubic_coeffs_torch(tx, cx);
+    int xs[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) xs[k] = min(max(ix - 1 + k, 0), W - 1);
+    double v = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      double h = (double)ldg_f(r[k] + xs[0]) * cx[0];
+      h = fma((double)ldg_f(r[k] + xs[1]), cx[1], h);
+      h = fma((double)ldg_f(r[k] + xs[2]), cx[2], h);
+      h = fma((double)ldg_f(r[k] + xs[3]), cx[3], h);
+      v = k == 0 ? h * cy[0] : fma(h, cy[k], v);
+    }
+    if (clamp01) v = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v);     // torch.clamp: a NaN stays a NaN
+    out[j] = (float)v;
+  }
+  float* d = a.dst[l] + row * Wo + ox0;
+  if (a.vec[l]) {
+    *(f32x4*)d = f32x4{out[0], out[1], out[2], out[3]};
+  } else {
+#pragma unroll
+    for (int j = 0; j < PYR_RUN; ++j)
+      if (ox0 + j < Wo) d[j] = out[j];
+  }
+}
+
 inline int rs_grid(long n) {
   long g = (n + 255) / 256;
   return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
@@ -115,6 +204,41 @@ int srhip_clip01(float* x, long n, void* stream) {
   SR_REQUIRE(x && n > 0, "clip01: empty");
   hipLaunchKernelGGL(k_clip01, dim3(rs_grid(n)), dim3(256), 0, (hipStream_t)stream, x, n);
   SR_LAUNCH_CHECK("clip01");
+  return 0;
+}
+
+int srhip_resize_bicubic_ac_pyramid(const float* src, int B, int H, int W, const srhip_pyr_level* levels, int n, int clamp01,
+                                    void* stream) {
+  SR_REQUIRE(src && levels && B > 0 && H > 0 && W > 0, "resize_bicubic_ac_pyramid: empty image / NULL argument");
+  SR_REQUIRE(H <= PYR_MAXDIM && W <= PYR_MAXDIM, "resize_bicubic_ac_pyramid: source larger than %d pixels a side", PYR_MAXDIM);
+  SR_REQUIRE(n >= 1 && n <= PYR_MAXL, "resize_bicubic_ac_pyramid: %d levels (1 .. %d per call)", n, PYR_MAXL);
+  const long src_bytes = (long)B * H * W * 4;
+  PyrArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = n;
+  long blk = 0;
+  for (int l = 0; l < n; ++l) {
+    const srhip_pyr_level& lv = levels[l];
+    SR_REQUIRE(lv.dst && lv.Ho > 0 && lv.Wo > 0, "resize_bicubic_ac_pyramid: level %d is empty / NULL", l);
+    SR_REQUIRE(lv.Ho <= PYR_MAXDIM && lv.Wo <= PYR_MAXDIM, "resize_bicubic_ac_pyramid: level %d larger than %d pixels a side", l,
+               PYR_MAXDIM);
+    const long bytes = (long)B * lv.Ho * lv.Wo * 4;
+    SR_REQUIRE(sr_disjoint(lv.dst, bytes, src, src_bytes), "resize_bicubic_ac_pyramid: level %d overlaps the source", l);
+    for (int m = 0; m < l; ++m)
+      SR_REQUIRE(sr_disjoint(lv.dst, bytes, levels[m].dst, (long)B * levels[m].Ho * levels[m].Wo * 4),
+                 "resize_bicubic_ac_pyramid: levels %d and %d overlap", m, l);
+    a.dst[l] = lv.dst;
+    a.Ho[l] = lv.Ho;
+    a.Wo[l] = lv.Wo;
+    a.runs[l] = sr_cdiv(lv.Wo, PYR_RUN);
+    a.vec[l] = lv.Wo % PYR_RUN == 0 && ((uintptr_t)lv.dst & 15) == 0;
+    a.blk0[l] = (int)blk;
+    blk += ((long)B * lv.Ho * a.runs[l] + 255) / 256;
+    SR_REQUIRE(blk < (1L << 31), "resize_bicubic_ac_pyramid: too many output pixels for one launch");
+  }
+  for (int l = n; l <= PYR_MAXL; ++l) a.blk0[l] = (int)blk;
+  hipLaunchKernelGGL(k_bicubic_ac_pyramid, dim3((unsigned)blk), dim3(256), 0, (hipStream_t)stream, src, B, H, W, a, clamp01);
+  SR_LAUNCH_CHECK("resize_bicubic_ac_pyramid");
   return 0;
 }
 

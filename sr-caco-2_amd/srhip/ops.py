@@ -1656,14 +1656,19 @@ def loss_l1l2(pred, target, mode, lam=1.0, weight=None, grad=None, loss_out=None
 
 
 def ssim_loss(pred, target, ws, lam=1.0, grad=None, loss_out=None, grad_accum=False,
-              loss_accum=False):
-    """pred/target [B,1,H,W] or [B,H,W]."""
+              loss_accum=False, workspace=None):
+    """pred/target [B,1,H,W] or [B,H,W].  workspace: a caller-owned float32 buffer of srhip_ssim_loss_ws(B, H, W) elements
+    (the multi-scale loss keeps one per level) instead of the shared scratch buffer."""
     _chk(pred, target, grad, loss_out)
     B = pred.shape[0]
     H, W = pred.shape[-2:]
     if loss_out is None:
         loss_out = torch.empty(1, device=pred.device, dtype=torch.float32)
-    wsb = SCRATCH.get("ssim_ws", lib.srhip_ssim_loss_ws(B, H, W), device=pred.device)
+    if workspace is None:
+        wsb = SCRATCH.get("ssim_ws", lib.srhip_ssim_loss_ws(B, H, W), device=pred.device)
+    else:
+        wsb = workspace
+        assert wsb.is_cuda and wsb.dtype == torch.float32 and wsb.numel() >= lib.srhip_ssim_loss_ws(B, H, W)
     call("srhip_ssim_loss", _p(pred), _p(target), _p(grad), _p(loss_out), _p(wsb), B, H, W, ws,
          float(lam), int(grad_accum), int(loss_accum), _st())
     return loss_out
@@ -1808,6 +1813,46 @@ def resize_cubic(src, size_hw, out=None):
         out = torch.empty(B, Ho, Wo, device=src.device, dtype=src.dtype)
     call("srhip_resize_cubic", _p(src), _p(out), int(src.dtype == torch.uint8), B, H, W, Ho, Wo, _st())
     return out
+
+
+class _PyrLevel(ctypes.Structure):   # srhip_pyr_level (include/srhip.h)
+    _fields_ = [("dst", ctypes.c_void_p), ("Ho", ctypes.c_int), ("Wo", ctypes.c_int)]
+
+
+PYR_MAX_LEVELS = 8
+
+
+def resize_bicubic_ac_pyramid(src, shapes, out=None, clamp=True):
+    """[torch.clamp(F.interpolate(src, size=s, mode="bicubic", align_corners=True), 0, 1) for s in shapes] for a batch of
+    1-channel float32 images [B, 1, H, W] or [B, H, W], every resized level in ONE launch (resize.hip; the resized targets
+    of the multi-scale losses, model_plain.py:257-264,298-305).  out: the level buffers (shape of src with (h, w) in the
+    last two dimensions; made here when None).  A level of the source's own size is not resized: the list holds ``src``
+    itself there and its ``out`` entry is left untouched -- with no other level there is no launch at all."""
+    if not src.is_cuda:
+        raise SrhipError("srhip ops need CUDA/HIP tensors (no CPU fallback exists)")
+    assert src.dim() in (3, 4) and (src.dim() == 3 or src.shape[1] == 1) and src.is_contiguous() \
+        and src.dtype == torch.float32, (src.shape, src.dtype)
+    B, (H, W) = src.shape[0], src.shape[-2:]
+    lead = tuple(src.shape[:-2])
+    shapes = [(int(s[0]), int(s[1])) for s in shapes]
+    if out is None:
+        out = [None if s == (H, W) else torch.empty(lead + s, device=src.device, dtype=torch.float32) for s in shapes]
+    assert len(out) == len(shapes)
+    res, todo = [], []
+    for s, o in zip(shapes, out):
+        if s == (H, W):
+            res.append(src)
+            continue
+        assert o.is_cuda and o.dtype == torch.float32 and o.is_contiguous() and tuple(o.shape) == lead + s, (o.shape, s)
+        res.append(o)
+        todo.append(o)
+    for i in range(0, len(todo), PYR_MAX_LEVELS):
+        part = todo[i:i + PYR_MAX_LEVELS]
+        lv = (_PyrLevel * len(part))()
+        for j, o in enumerate(part):
+            lv[j].dst, lv[j].Ho, lv[j].Wo = o.data_ptr(), o.shape[-2], o.shape[-1]
+        call("srhip_resize_bicubic_ac_pyramid", _p(src), B, H, W, ctypes.addressof(lv), len(part), int(bool(clamp)), _st())
+    return res
 
 
 def u8_to_unit(src, out=None):

@@ -499,6 +499,44 @@ class TrainStep:
         if self.world > 1 and self._live_buffers:
             broadcast_replica_state(None, self._live_buffers, self.pg)
 
+    def _term(self, t, y, target, weight, dy, part, lam, first, ssim_ws=None):
+        """ONE term of the MasterLoss on ONE image: the kernel call of the term table that loss_and_grad and
+        multiscale_loss_and_grad share.  lam: the term's lambda (the multi-scale rules divide it by the number of images);
+        part: the one-element slot of its value; first: this term writes dy, later ones accumulate into it."""
+        if t[0] in ("l1", "l2"):
+            ops.loss_l1l2(y, target, 0 if t[0] == "l1" else 1, lam, weight if t[0] == "l1" else None, dy,
+                          part, grad_accum=not first)
+        elif t[0] == "ssim":
+            if ssim_ws is None:
+                ops.ssim_loss(y, target, t[2], lam, dy, part, grad_accum=not first)
+            else:
+                ops.ssim_loss(y, target, t[2], lam, dy, part, grad_accum=not first, workspace=ssim_ws)
+        elif t[0] == "charbonnier":
+            ops.loss_pointwise(y, target, 2, lam, t[2], None, dy, part, grad_accum=not first)
+        elif t[0] == "boundpred":       # (kind, lam, eps, ELB module | t, restore_range, color_max)
+            tb = float(t[3].get_t()) if hasattr(t[3], "get_t") else float(t[3])
+            ops.loss_bounded(y, target, lam, t[2], tb, float(t[5]) if t[4] else 1.0, dy, part,
+                             grad_accum=not first)
+        elif t[0] == "w_sparsity":      # value here; its gradient is added after backward (step())
+            ops.l1_sparsity(self.fp.flat, lam, None, part)
+            if first:
+                dy.zero_()
+        elif t[0] == "kde":
+            ops.loss_kde(y, target, lam, t[2], t[3], t[4], dy, part, grad_accum=not first,
+                         elb_t=float(t[5].get_t()) if (t[2] == 4 and len(t) > 5) else 1.0)
+        elif t[0] == "hist":
+            ops.loss_hist(y, target, lam, t[2], t[3], t[4], dy, part, grad_accum=not first,
+                          elb_t=float(t[5].get_t()) if (t[2] == 4 and len(t) > 5) else 1.0)
+        elif t[0] == "local_moments":
+            ops.loss_local_moments(y, target, lam, dy, part, grad_accum=not first)
+        elif t[0] == "l2sum":
+            ops.loss_pointwise(y, target, 3, lam, grad=dy, loss_out=part, grad_accum=not first)
+        elif t[0].replace("norm_", "") in ops.STENCIL_OPS:
+            ops.loss_stencil(y, target, t[0].replace("norm_", ""), lam, t[2], t[3] if len(t) > 3 else 3,
+                             t[0].startswith("norm_"), dy, part, grad_accum=not first)
+        else:
+            raise NotImplementedError(t[0])
+
     def loss_and_grad(self, y, target, weight=None):
         """MasterLoss value(s) + d loss / d y through the fused loss kernels.  weight: the per-pixel weights of the
         target (--ppiw, dataset_dpsr.py:925-928); only L1 consumes them (dlib/loss/main.py:45-76)."""
@@ -506,62 +544,53 @@ class TrainStep:
             self.dy = torch.empty_like(y)
         lb = self.loss_buf
         for i, t in enumerate(self.loss_terms):
-            first = i == 0
-            part = lb[1 + i:2 + i]
-            if t[0] in ("l1", "l2"):
-                ops.loss_l1l2(y, target, 0 if t[0] == "l1" else 1, t[1], weight if t[0] == "l1" else None, self.dy,
-                              part, grad_accum=not first)
-            elif t[0] == "ssim":
-                ops.ssim_loss(y, target, t[2], t[1], self.dy, part, grad_accum=not first)
-            elif t[0] == "charbonnier":
-                ops.loss_pointwise(y, target, 2, t[1], t[2], None, self.dy, part, grad_accum=not first)
-            elif t[0] == "boundpred":       # (kind, lam, eps, ELB module | t, restore_range, color_max)
-                tb = float(t[3].get_t()) if hasattr(t[3], "get_t") else float(t[3])
-                ops.loss_bounded(y, target, t[1], t[2], tb, float(t[5]) if t[4] else 1.0, self.dy, part,
-                                 grad_accum=not first)
-            elif t[0] == "w_sparsity":      # value here; its gradient is added after backward (step())
-                ops.l1_sparsity(self.fp.flat, t[1], None, part)
-                if first:
-                    self.dy.zero_()
-            elif t[0] == "kde":
-                ops.loss_kde(y, target, t[1], t[2], t[3], t[4], self.dy, part, grad_accum=not first,
-                             elb_t=float(t[5].get_t()) if (t[2] == 4 and len(t) > 5) else 1.0)
-            elif t[0] == "hist":
-                ops.loss_hist(y, target, t[1], t[2], t[3], t[4], self.dy, part, grad_accum=not first,
-                              elb_t=float(t[5].get_t()) if (t[2] == 4 and len(t) > 5) else 1.0)
-            elif t[0] == "local_moments":
-                ops.loss_local_moments(y, target, t[1], self.dy, part, grad_accum=not first)
-            elif t[0] == "l2sum":
-                ops.loss_pointwise(y, target, 3, t[1], grad=self.dy, loss_out=part, grad_accum=not first)
-            elif t[0].replace("norm_", "") in ops.STENCIL_OPS:
-                ops.loss_stencil(y, target, t[0].replace("norm_", ""), t[1], t[2], t[3] if len(t) > 3 else 3,
-                                 t[0].startswith("norm_"), self.dy, part, grad_accum=not first)
-            else:
-                raise NotImplementedError(t[0])
+            self._term(t, y, target, weight, self.dy, lb[1 + i:2 + i], t[1], i == 0)
         return self.dy
 
-    def multiscale_loss_and_grad(self, y, inter, target):
-        """loss_mslaprs (reference model_plain.py:277-314): the loss of the output plus the same loss of every
-        intermediate image against the bicubically resized target (align_corners=True, clamped to [0, 1]; stock
-        F.interpolate, as the reference), all divided by the number of images.  L1 / L2 terms."""
-        import torch.nn.functional as F
-        n = len(inter) + 1.0
-        for t in self.loss_terms:
-            if t[0] not in ("l1", "l2"):
-                raise NotImplementedError(f"multi-scale loss (intermediate outputs) with the term {t[0]!r}: l1 / l2 only")
+    def multiscale_loss_and_grad(self, y, inter, target, weight=None):
+        """The three multi-image rules of the reference's trainer: loss_mslaprs / loss_prosr (model_plain.py:277-314,
+        236-275: the MasterLoss of the output plus that of every intermediate image against the bicubically resized target,
+        align_corners=True, clamped to [0, 1]) and loss_srfbn with use_cl (:202-232: every pass's prediction against the
+        SAME target), each divided by the number of images n.  Every enabled term runs on every image with lam / n through
+        the term table of loss_and_grad (_term); image j's gradient goes to its own buffer, its values to parts[j].
+        The resized targets are one launch (ops.resize_bicubic_ac_pyramid); images of the target's size take the target.
+        w_sparsity does not depend on the image: the reference adds lam * sum|w| once per image and divides by n, so it
+        enters ONCE with its full lam (value here, gradient behind backward as in the single-image step).
+        weight (--ppiw; L1 only): where every image has the target's shape (SRFBN).  Buffers are kept per shape set."""
         outs = [y] + list(inter)
-        tgts = [target] + [torch.clamp(F.interpolate(target, size=t.shape[2:], mode="bicubic", align_corners=True),
-                                       0.0, 1.0) for t in inter]
-        if getattr(self, "_ms", None) is None or len(self._ms[0]) != len(outs) or \
-                any(a.shape != b.shape for a, b in zip(self._ms[0], outs)):
-            self._ms = ([torch.empty_like(o) for o in outs],
-                        torch.zeros(len(outs), len(self.loss_terms), device=y.device))
-        dys, parts = self._ms
+        n = float(len(outs))
+        if weight is not None:
+            if any(o.shape[-2:] != target.shape[-2:] for o in outs):
+                raise NotImplementedError(
+                    "per-pixel weights with the multi-scale loss: an intermediate image is smaller than the weight map, and "
+                    "the reference itself fails there on the shape mismatch (L1 multiplies the level's |y - target| by the "
+                    "full-size trg_per_pixel_weight, dlib/loss/main.py:45-76); weights go with same-size images only (SRFBN)")
+            assert weight.shape == target.shape and weight.is_contiguous(), "per-pixel weights: the target's shape"
+        terms = self.loss_terms
+        ms = getattr(self, "_ms", None)
+        if ms is None or len(ms["dy"]) != len(outs) or any(a.shape != b.shape for a, b in zip(ms["dy"], outs)):
+            same = [o.shape[-2:] == target.shape[-2:] for o in outs]
+            ssim = any(t[0] == "ssim" for t in terms)
+            ms = self._ms = {
+                "dy": [torch.empty_like(o) for o in outs],
+                "parts": torch.zeros(len(outs), len(terms), device=y.device),
+                # the resized targets (None: the target itself) and one SSIM workspace per level
+                "tgt": [None if sm else torch.empty(target.shape[:-2] + o.shape[-2:], device=y.device)
+                        for sm, o in zip(same, outs)],
+                "ssim_ws": [torch.empty(ops.lib.srhip_ssim_loss_ws(o.shape[0], *o.shape[-2:]), device=y.device)
+                            if ssim else None for o in outs]}
+        dys, parts = ms["dy"], ms["parts"]
+        tgts = ops.resize_bicubic_ac_pyramid(target, [o.shape[-2:] for o in outs], out=ms["tgt"], clamp=True)
         for j, (o, tg) in enumerate(zip(outs, tgts)):
-            for i, t in enumerate(self.loss_terms):
-                ops.loss_l1l2(o, tg.contiguous(), 0 if t[0] == "l1" else 1, t[1] / n, None, dys[j], parts[j, i:i + 1],
-                              grad_accum=i > 0)
-        self.loss_buf[1:1 + len(self.loss_terms)].copy_(parts.sum(0))
+            for i, t in enumerate(terms):
+                if t[0] == "w_sparsity":
+                    if j == 0:
+                        self._term(t, o, tg, None, dys[j], parts[j, i:i + 1], t[1], i == 0)
+                    elif i == 0:
+                        dys[j].zero_()
+                    continue
+                self._term(t, o, tg, weight, dys[j], parts[j, i:i + 1], t[1] / n, i == 0, ssim_ws=ms["ssim_ws"][j])
+        torch.sum(parts, 0, out=self.loss_buf[1:1 + len(terms)])
         return dys[0], dys[1:]
 
     def step_graph(self, lr_img, hr_img, weight=None):
@@ -638,10 +667,8 @@ class TrainStep:
             ops.axpby(y, y, self.inv_range, 0.0)
         inter = getattr(net.engine, "intermediate_outs", None)
         d_inter = None
-        if inter:       # MSLapSRN: the trainer's multi-scale loss (model_plain.py:277-314)
-            if weight is not None:
-                raise NotImplementedError("per-pixel weights with the multi-scale loss")
-            dy, d_inter = self.multiscale_loss_and_grad(y, inter, hr_img)
+        if inter:       # MSLapSRN / ProSR / SRFBN: the trainer's multi-image losses (model_plain.py:202-314)
+            dy, d_inter = self.multiscale_loss_and_grad(y, inter, hr_img, weight)
         else:
             if weight is not None:
                 assert weight.shape == hr_img.shape and weight.is_contiguous(), "per-pixel weights: the target's shape"
