@@ -1,7 +1,9 @@
 """fp16-storage convs of the evaluation path (conv_h16.hip, include/srhip.h srhip_conv3x3_nhwc_h16 / _cin1_h16 / _cout1_h16)
 against float64 aten on the SAME rounded operands: the fp16 activations as they are, the weight as the leading fp16 plane under
 its per-output-channel power-of-two scale (emulated here), so that what remains is the f32 accumulation order and the final
-rounding of the result to fp16 (2^-11 relative)."""
+rounding of the result to fp16 (2^-11 relative).
+Every shape here gives fewer than 1024 8 x 16 tiles, so these cases run the 4-row tile (RW = 2) and one pass of the head / tail
+kernels; the 8-row tile (RW = 4) and the grid-stride passes are tested in tests/test_gpu_h16_tile_forms.py."""
 import pytest
 import torch
 import torch.nn.functional as F
