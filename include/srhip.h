@@ -377,7 +377,9 @@ int srhip_gemm_tn(const float* A, long lda, const float* B, long ldb, int M, int
                   float* part, float* part_colsum, int S, void* stream);
 /* Several Linear weight-gradient problems over the same M rows in one launch, each with its own partial buffers:
  * up to 4 (exact-f32 kernels: the four Linears of a Swin block) or up to 24 (_bx3: the 4 x depth Linears of a whole
- * RSTB layer -- more tiles per launch need fewer reduce slices S to fill the chip). */
+ * RSTB layer -- more tiles per launch need fewer reduce slices S to fill the chip).  M > 0 and S > 0 (the caller's choice;
+ * srhip_tn_group_plan proposes one): slice s takes rows [s, s + 1) * ceil(ceil(M / S) / 32) * 32, a slice past row M
+ * holds zeros. */
 typedef struct srhip_tn_problem {
   const float* A; long lda;          /* dY [M][NI] */
   const float* B; long ldb;          /* X  [M][NJ] */

@@ -405,12 +405,14 @@ int srhip_tn_group_plan(int M, int ntiles, int* S) { return sr_tn_group_plan(M, 
 
 static int gemm_tn_grouped_any(bool bx, const srhip_tn_problem* probs, int nprob, int M, int S, void* stream) {
   SR_REQUIRE(nprob >= 1 && nprob <= (bx ? 24 : 4), "gemm_tn_grouped: 1..%d problems", bx ? 24 : 4);
+  SR_REQUIRE(M > 0 && S > 0, "gemm_tn_grouped: empty problem");     // (the launchers divide M by S)
   TnArgs a[24];
   memset(a, 0, sizeof(a));
   for (int k = 0; k < nprob; ++k) {
     const srhip_tn_problem& q = probs[k];
     SR_REQUIRE(q.b_mode >= 0 && q.b_mode <= 2, "gemm_tn_grouped: b_mode %d", q.b_mode);
     SR_REQUIRE(q.b_mode != 1 || q.ln_stats, "gemm_tn_grouped: layernorm prologue without stats");
+    SR_REQUIRE(!q.a_rowscale || q.a_rowscale_rows > 0, "gemm_tn_grouped: a_rowscale_rows must be > 0");
     TnArgs& p = a[k];
     p.A = q.A; p.lda = q.lda; p.B = q.B; p.ldb = q.ldb; p.M = M; p.NI = q.NI; p.NJ = q.NJ;
     p.a_rowscale = q.a_rowscale; p.a_rowscale_rows = q.a_rowscale_rows; p.b_mode = q.b_mode;

@@ -126,6 +126,36 @@ def test_plan_queries_need_no_gpu():
         S, per = ctypes.c_int(0), ctypes.c_long(0)
         ops.call("srhip_conv3x3_wgrad_batched_plan", k, B, H, W, Co, Ci, ctypes.addressof(S), ctypes.addressof(per))
         assert (S.value, per.value) == want, (k, B, H, W, Co, Ci)
+    # the grouped Linear weight gradient: tile counts by pick_tile's classes (180 | <= 64 | <= 128 or a multiple of 128 | 192),
+    # the README layer group (six blocks of 3 + 2 + 2 + 1 tiles) at S = 5 on the bf16x3 launch, the workspace of the
+    # LayerNorm-folded reducers (four rows per row block, two K-vectors each), and the refusals that precede any launch
+    tiles = {(540, 180): 3, (180, 360): 2, (360, 180): 2, (180, 180): 1, (180, 60): 1, (60, 120): 1, (384, 128): 3,
+             (128, 256): 2, (64, 64): 1, (48, 20): 1, (184, 180): 1, (180, 200): 2, (200, 68): 2, (360, 184): 2, (400, 68): 3}
+    for (NI, NJ), want in tiles.items():
+        assert ops.lib.srhip_tn_tiles(NI, NJ) == want, (NI, NJ)
+    layer = 6 * sum(tiles[k] for k in ((540, 180), (180, 360), (360, 180), (180, 180)))
+    assert layer == 48
+    for (M, nt, sfx), want in {(32768, 48, "_bx3"): 5, (2077, 48, "_bx3"): 5, (2077, 47, "_bx3"): 5, (2077, 8, "_bx3"): 17,
+                               (2077, 3, "_bx3"): 17, (100, 48, "_bx3"): 1, (32768, 1, "_bx3"): 256, (32768, 8, ""): 64,
+                               (2077, 8, ""): 17, (32768, 600, ""): 1}.items():
+        S = ctypes.c_int(0)
+        ops.call("srhip_tn_group_plan" + sfx, M, nt, ctypes.addressof(S))
+        assert S.value == want, (M, nt, sfx)
+    for N, K in ((180, 180), (540, 180), (60, 120), (20, 48), (4, 4), (6, 5)):
+        assert ops.lib.srhip_ln_affine_ws(N, K) == -(-N // 4) * 2 * K >= -(-N // 16) * 2 * K
+    tn, red = (ops._TnProblem * 25)(), (ops._ReduceProblem * 25)()
+    for name, arr, n, S in (("srhip_gemm_tn_grouped_bx3", tn, 25, 2), ("srhip_gemm_tn_grouped", tn, 5, 2),
+                            ("srhip_gemm_tn_grouped_bx3", tn, 0, 2), ("srhip_gemm_tn_grouped_bx3", tn, 1, 0),
+                            ("srhip_reduce_wgrad_grouped", red, 25, 2), ("srhip_reduce_wgrad_grouped", red, 1, 0),
+                            ("srhip_reduce_wgrad_grouped", red, 1, 2)):      # (the last: a problem without buffers)
+        with pytest.raises(ops.SrhipError):
+            ops.call(name, ctypes.addressof(arr), n, 64, S, None) if arr is tn else ops.call(name, ctypes.addressof(arr), n, S, None)
+    tn[0].b_mode = 3
+    with pytest.raises(ops.SrhipError, match="b_mode 3"):
+        ops.call("srhip_gemm_tn_grouped_bx3", ctypes.addressof(tn), 1, 64, 2, None)
+    tn[0].b_mode = 1
+    with pytest.raises(ops.SrhipError, match="without stats"):
+        ops.call("srhip_gemm_tn_grouped", ctypes.addressof(tn), 1, 64, 2, None)
 
 
 def test_cpu_tensors_fail_loudly():
