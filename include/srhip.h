@@ -468,6 +468,21 @@ int srhip_resize_cubic(const void* src, void* dst, int is_u8, int B, int H, int 
 int srhip_u8_to_unit(const unsigned char* src, float* dst, long n, void* stream);
 int srhip_clip01(float* x, long n, void* stream);
 
+/* ---- util.imresize_np(img, scale, antialiasing=True) on 1-channel images (resize.hip): the LR image of an HR-only pair --- */
+/* dlib/utils/utils_image.py:1358-1422 (cubic, calculate_weights_indices), :1505-1578 (imresize_np), called by the dataset for
+ * a pair without a true low-resolution tile that is not a CACO-2 tile (dlib/datasets/dataset_dpsr.py:798-824): MATLAB-style
+ * antialiased bicubic down-scaling.  src: B images [H][W], uint8 (is_u8; read as np.float32(v / 255.), as
+ * srhip_patch_gather does) or float32; dst: B float32 images [Ho][Wo], Ho = ceil(H * scale), Wo = ceil(W * scale),
+ * 1/64 <= scale < 1; tmp: B * Ho * W floats of scratch (the image after the rows pass, which the reference rounds to
+ * float32 as well).  The cubic kernel (a = -0.5) is stretched by 1 / scale over ceil(4 / scale) + 2 taps whose weights are
+ * normalised per output pixel; taps outside the image mirror about the border (edge pixel repeated); a tap of zero weight
+ * is never read.  Weights, coordinates and sums in f64, rounded once per pass; bit-identical from run to run.  An image
+ * so small that a tap of non-zero weight would mirror past the OPPOSITE border (8 x 8 at 1/8) is refused.  Rows whose
+ * length is a multiple of 4 on 16-byte aligned buffers move as 16-byte accesses, others as scalars.  Two launches (rows,
+ * then columns).  src, tmp and dst must not overlap. */
+int srhip_imresize_aa(const void* src, int is_u8, float* tmp, float* dst, int B, int H, int W, int Ho, int Wo, double scale,
+                      void* stream);
+
 /* ---- the target pyramid of the multi-scale training losses, one launch (resize.hip) ------------------------------ */
 /* loss_prosr / loss_mslaprs (dlib/models/model_plain.py:257-264,298-305): every intermediate image is compared with
  * torch.clamp(F.interpolate(H, size = its size, mode = 'bicubic', align_corners = True), 0, 1).  src: B images [H][W],
@@ -801,6 +816,14 @@ typedef struct {
   int H, W, y0, x0, mode;
 } srhip_patch_job;
 int srhip_patch_gather(const srhip_patch_job* jobs, int B, int P, float* out, void* stream);
+/* The same crop / augment_img mode / [B][1][P][P] layout out of resident FLOAT32 tiles: the low-resolution tile of an HR-only
+ * pair stays the float image util.imresize_np returned (dlib/datasets/dataset_dpsr.py:810,872-873,893).  A pure copy:
+ * bit-exact.  jobs is a HOST array. */
+typedef struct {
+  const float* img;           /* device pointer */
+  int H, W, y0, x0, mode;
+} srhip_patch_job_f32;
+int srhip_patch_gather_f32(const srhip_patch_job_f32* jobs, int B, int P, float* out, void* stream);
 /* ROI-weighted patch origins, the 'roi' sampler of the training crops (PatchSampler._roi,
  * dataset_dpsr.py:330-369): origin (r, c) of the (H-P) x (W-P) candidates has probability
  * proportional to exp(5*roi) + 1, roi = img[r + P/2][c + P/2] >= threshold.  One uniform in [0,1)

@@ -43,6 +43,22 @@ __global__ void __launch_bounds__(256) k_patch_gather(PatchJobs jobs, int P, flo
   }
 }
 
+// The same crop / augmentation out of a resident FLOAT32 tile: the low-resolution tile of an HR-only pair, which the reference
+// keeps as the float result of util.imresize_np (dataset_dpsr.py:810,872-873,893).  A pure copy: bit-exact.
+struct PatchJobsF32 {
+  struct J { const float* img; int W, y0, x0, mode; } j[MAXJOBS];
+};
+__global__ void __launch_bounds__(256) k_patch_gather_f32(PatchJobsF32 jobs, int P, float* __restrict__ out) {
+  const PatchJobsF32::J J = jobs.j[blockIdx.y];
+  float* o = out + (long)blockIdx.y * P * P;
+  for (int idx = blockIdx.x * 256 + threadIdx.x; idx < P * P; idx += gridDim.x * 256) {
+    const int i = idx / P, j = idx - i * P;
+    int si, sj;
+    aug_src(J.mode, i, j, P, si, sj);
+    o[idx] = J.img[(long)(J.y0 + si) * J.W + J.x0 + sj];
+  }
+}
+
 // ROI-weighted patch origins (PatchSampler._roi, dataset_dpsr.py:330-369): over the (H-P) x (W-P)
 // candidate origins, origin (r, c) has weight exp(5 * roi) + 1 with roi = img[r + P/2][c + P/2] >= th,
 // i.e. e^5 + 1 on the region of interest and 2 elsewhere; the reference draws one multinomial
@@ -173,5 +189,29 @@ extern "C" int srhip_patch_gather(const srhip_patch_job* jobs, int B, int P, flo
     hipLaunchKernelGGL(k_patch_gather, dim3(gx, nb), dim3(256), 0, st, pj, P, out + (long)b0 * P * P);
   }
   SR_LAUNCH_CHECK("patch_gather");
+  return 0;
+}
+
+extern "C" int srhip_patch_gather_f32(const srhip_patch_job_f32* jobs, int B, int P, float* out, void* stream) {
+  SR_REQUIRE(jobs && out && B > 0 && P > 0, "patch_gather_f32: empty batch / NULL argument");
+  for (int b = 0; b < B; ++b) {
+    const srhip_patch_job_f32& q = jobs[b];
+    SR_REQUIRE(q.img != nullptr, "patch_gather_f32: job %d has no image", b);
+    SR_REQUIRE(q.mode >= 0 && q.mode <= 7, "patch_gather_f32: job %d: augmentation mode %d (0..7)", b, q.mode);
+    SR_REQUIRE(q.y0 >= 0 && q.x0 >= 0 && q.y0 + P <= q.H && q.x0 + P <= q.W,
+               "patch_gather_f32: job %d: crop (%d,%d)+%d outside the %dx%d tile", b, q.y0, q.x0, P, q.H, q.W);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  for (int b0 = 0; b0 < B; b0 += MAXJOBS) {
+    const int nb = B - b0 < MAXJOBS ? B - b0 : MAXJOBS;
+    PatchJobsF32 pj;
+    for (int b = 0; b < nb; ++b) {
+      const srhip_patch_job_f32& q = jobs[b0 + b];
+      pj.j[b].img = q.img; pj.j[b].W = q.W; pj.j[b].y0 = q.y0; pj.j[b].x0 = q.x0; pj.j[b].mode = q.mode;
+    }
+    const int gx = sr_cdiv((long)P * P, 256) < 64 ? sr_cdiv((long)P * P, 256) : 64;
+    hipLaunchKernelGGL(k_patch_gather_f32, dim3(gx, nb), dim3(256), 0, st, pj, P, out + (long)b0 * P * P);
+  }
+  SR_LAUNCH_CHECK("patch_gather_f32");
   return 0;
 }

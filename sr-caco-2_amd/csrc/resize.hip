@@ -172,6 +172,159 @@ __global__ void __launch_bounds__(256) k_bicubic_ac_pyramid(const float* __restr
   }
 }
 
+// ---- util.imresize_np(img, scale, antialiasing=True), scale < 1: MATLAB-style antialiased bicubic down-scaling -------------
+// dlib/utils/utils_image.py:1358-1422 (cubic, calculate_weights_indices), :1505-1578 (imresize_np); the low-resolution image
+// of an HR-only pair (dataset_dpsr.py:798-824).  Along each axis output pixel o (1-based x = o + 1) sits at the input
+// coordinate u = x / scale + (1 - 1 / scale) / 2; its taps are the P = ceil(4 / scale) + 2 pixels from floor(u - 2 / scale)
+// on, weighted by scale * cubic((u - i) * scale) (the Keys kernel, a = -0.5, stretched by 1 / scale) and normalised to sum
+// 1; a tap outside the image is mirrored about the border with the edge pixel repeated.  Rows first (contraction over H)
+// into an f32 intermediate [B][Ho][W], then columns: the reference stores out_1 in float32, so does this.  Coordinates,
+// weights and sums are f64, rounded once per pass; every weight is recomputed from the output index, so there is no table
+// and nothing to reduce across threads: bit-identical from run to run.
+//
+// Two launches, one per axis.  The rows pass has one thread per 4 consecutive columns of one output row: its taps are rows
+// of the source, so a wave reads and writes whole contiguous row segments (16 bytes a lane when the rows allow).  The columns
+// pass has one thread per 4 consecutive output pixels, which walk the same intermediate row 4 / scale floats apart: those
+// loads are strided, the row segment a wave covers stays in L1 / L2 for all of its taps, and the store is 16 bytes a lane.
+constexpr int AA_RUN = 4;          // pixels per thread: one 16-byte access
+constexpr int AA_MAXDIM = 32768;   // image edge
+constexpr int AA_MAXTAPS = 258;    // ceil(4 / scale) + 2 at scale = 1 / 64
+
+__host__ __device__ inline double aa_cubic(double x) {
+#pragma clang fp contract(off)
+  const double a = fabs(x), a2 = a * a, a3 = a2 * a;
+  if (a <= 1.0) return 1.5 * a3 - 2.5 * a2 + 1.0;
+  if (a <= 2.0) return -0.5 * a3 + 2.5 * a2 - 4.0 * a + 2.0;
+  return 0.0;
+}
+// input coordinate (1-based) of output pixel o and its left-most tap (1-based)
+__host__ __device__ inline int aa_left(int o, double scale, double& u) {
+#pragma clang fp contract(off)
+  u = (double)(o + 1) / scale + 0.5 * (1.0 - 1.0 / scale);
+  return (int)floor(u - (4.0 / scale) / 2.0);
+}
+// un-normalised weight of tap k
+__host__ __device__ inline double aa_weight(double u, int left, int k, double scale) {
+#pragma clang fp contract(off)
+  return scale * aa_cubic((u - (double)(left + k)) * scale);
+}
+// 0-based source index of tap k, mirrored about the borders with the edge repeated; outside [0, n) only when the tap lies
+// more than n pixels beyond a border
+__host__ __device__ inline int aa_index(int left, int k, int n) {
+  const int j = left + k - 1;
+  return j < 0 ? -j - 1 : (j >= n ? 2 * n - 1 - j : j);
+}
+__host__ __device__ inline double aa_weight_sum(double u, int left, int P, double scale) {
+#pragma clang fp contract(off)
+  double s = 0.0;
+  for (int k = 0; k < P; ++k) s += aa_weight(u, left, k, scale);
+  return s;
+}
+// every tap of non-zero weight mirrors into the image (the kernels skip the others)
+inline bool aa_axis_fits(int n_in, int n_out, int P, double scale) {
+  for (int o = 0; o < n_out; ++o) {
+    double u;
+    const int left = aa_left(o, scale, u);
+    const double ws = aa_weight_sum(u, left, P, scale);
+    for (int k = 0; k < P; ++k) {
+      if (aa_weight(u, left, k, scale) / ws == 0.0) continue;
+      const int j = aa_index(left, k, n_in);
+      if (j < 0 || j >= n_in) return false;
+    }
+  }
+  return true;
+}
+
+template <bool U8, bool VEC>
+__global__ void __launch_bounds__(256) k_imresize_aa_rows(const void* __restrict__ srcv, float* __restrict__ tmp, int B, int H,
+                                                          int W, int Ho, double scale, int P) {
+#pragma clang fp contract(off)
+  const int runs = (W + AA_RUN - 1) / AA_RUN;
+  const long item = blockIdx.x * 256L + threadIdx.x;
+  if (item >= (long)B * Ho * runs) return;
+  const int x0 = (int)(item % runs) * AA_RUN;
+  const long row = item / runs;                 // b * Ho + oy
+  const int oy = (int)(row % Ho);
+  const long img = (row / Ho) * (long)H * W;
+  double u;
+  const int left = aa_left(oy, scale, u);
+  const double ws = aa_weight_sum(u, left, P, scale);
+  double acc[AA_RUN] = {0.0, 0.0, 0.0, 0.0};
+  for (int k = 0; k < P; ++k) {
+    const double w = aa_weight(u, left, k, scale) / ws;
+    if (w == 0.0) continue;                     // its mirrored row may lie outside a small image: never dereferenced
+    const int j = min(max(aa_index(left, k, H), 0), H - 1);     // in range already: the entry point refuses shapes where not
+    const long off = img + (long)j * W + x0;
+    float v[AA_RUN];
+    if (U8) {
+      const unsigned char* p = (const unsigned char*)srcv + off;
+      if (VEC) {
+        const unsigned q = *(const unsigned*)p;
+#pragma unroll
+        for (int e = 0; e < AA_RUN; ++e) v[e] = (float)((double)((q >> (8 * e)) & 255u) / 255.0);
+      } else {
+#pragma unroll
+        for (int e = 0; e < AA_RUN; ++e) v[e] = x0 + e < W ? (float)((double)p[e] / 255.0) : 0.f;
+      }
+    } else {
+      const float* p = (const float*)srcv + off;
+      if (VEC) {
+        const f32x4 q = ldg_f4(p);
+        v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
+      } else {
+#pragma unroll
+        for (int e = 0; e < AA_RUN; ++e) v[e] = x0 + e < W ? ldg_f(p + e) : 0.f;
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < AA_RUN; ++e) acc[e] += w * (double)v[e];
+  }
+  float* d = tmp + row * W + x0;
+  if (VEC) {
+    *(f32x4*)d = f32x4{(float)acc[0], (float)acc[1], (float)acc[2], (float)acc[3]};
+  } else {
+#pragma unroll
+    for (int e = 0; e < AA_RUN; ++e)
+      if (x0 + e < W) d[e] = (float)acc[e];
+  }
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(256) k_imresize_aa_cols(const float* __restrict__ tmp, float* __restrict__ dst, long rows, int W,
+                                                          int Wo, double scale, int P) {
+#pragma clang fp contract(off)
+  const int runs = (Wo + AA_RUN - 1) / AA_RUN;
+  const long item = blockIdx.x * 256L + threadIdx.x;
+  if (item >= rows * runs) return;
+  const int ox0 = (int)(item % runs) * AA_RUN;
+  const long row = item / runs;                 // b * Ho + oy
+  const float* src = tmp + row * W;
+  float out[AA_RUN];
+#pragma unroll
+  for (int e = 0; e < AA_RUN; ++e) {
+    const int ox = min(ox0 + e, Wo - 1);        // a ragged row's last run recomputes its last pixel; stored once below
+    double u;
+    const int left = aa_left(ox, scale, u);
+    const double ws = aa_weight_sum(u, left, P, scale);
+    double acc = 0.0;
+    for (int k = 0; k < P; ++k) {
+      const double w = aa_weight(u, left, k, scale) / ws;
+      if (w == 0.0) continue;
+      const int j = min(max(aa_index(left, k, W), 0), W - 1);
+      acc += w * (double)ldg_f(src + j);
+    }
+    out[e] = (float)acc;
+  }
+  float* d = dst + row * Wo + ox0;
+  if (VEC) {
+    *(f32x4*)d = f32x4{out[0], out[1], out[2], out[3]};
+  } else {
+#pragma unroll
+    for (int e = 0; e < AA_RUN; ++e)
+      if (ox0 + e < Wo) d[e] = out[e];
+  }
+}
+
 inline int rs_grid(long n) {
   long g = (n + 255) / 256;
   return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
@@ -239,6 +392,41 @@ int srhip_resize_bicubic_ac_pyramid(const float* src, int B, int H, int W, const
   for (int l = n; l <= PYR_MAXL; ++l) a.blk0[l] = (int)blk;
   hipLaunchKernelGGL(k_bicubic_ac_pyramid, dim3((unsigned)blk), dim3(256), 0, (hipStream_t)stream, src, B, H, W, a, clamp01);
   SR_LAUNCH_CHECK("resize_bicubic_ac_pyramid");
+  return 0;
+}
+
+int srhip_imresize_aa(const void* src, int is_u8, float* tmp, float* dst, int B, int H, int W, int Ho, int Wo, double scale,
+                      void* stream) {
+  SR_REQUIRE(src && tmp && dst && B > 0 && H > 0 && W > 0, "imresize_aa: empty image / NULL argument");
+  SR_REQUIRE(scale > 0.0 && scale < 1.0 && scale >= 1.0 / 64, "imresize_aa: scale %g (antialiased down-scaling: 1/64 <= scale < 1)",
+             scale);
+  SR_REQUIRE(H <= AA_MAXDIM && W <= AA_MAXDIM, "imresize_aa: source larger than %d pixels a side", AA_MAXDIM);
+  SR_REQUIRE(Ho == (int)ceil(H * scale) && Wo == (int)ceil(W * scale), "imresize_aa: output %dx%d is not ceil(%dx%d * %g)", Ho, Wo,
+             H, W, scale);
+  const int P = (int)ceil(4.0 / scale) + 2;
+  SR_REQUIRE(P <= AA_MAXTAPS, "imresize_aa: %d taps (at most %d)", P, AA_MAXTAPS);
+  SR_REQUIRE(aa_axis_fits(H, Ho, P, scale) && aa_axis_fits(W, Wo, P, scale),
+             "imresize_aa: a %dx%d image is too small for scale %g: a tap would mirror past the opposite border", H, W, scale);
+  const long src_bytes = (long)B * H * W * (is_u8 ? 1 : 4), tmp_bytes = (long)B * Ho * W * 4, dst_bytes = (long)B * Ho * Wo * 4;
+  SR_REQUIRE(sr_disjoint(tmp, tmp_bytes, src, src_bytes) && sr_disjoint(dst, dst_bytes, src, src_bytes) &&
+             sr_disjoint(dst, dst_bytes, tmp, tmp_bytes), "imresize_aa: src, tmp and dst overlap");
+  const long n1 = ((long)B * Ho * sr_cdiv(W, AA_RUN) + 255) / 256, n2 = ((long)B * Ho * sr_cdiv(Wo, AA_RUN) + 255) / 256;
+  SR_REQUIRE(n1 < (1L << 31) && n2 < (1L << 31), "imresize_aa: too many pixels for one launch");
+  hipStream_t st = (hipStream_t)stream;
+  // 16-byte accesses where every row starts on one: whole runs per row and aligned bases (4 bytes for a uint8 source)
+  const bool v1 = W % AA_RUN == 0 && ((uintptr_t)src & (is_u8 ? 3 : 15)) == 0 && ((uintptr_t)tmp & 15) == 0;
+  const bool v2 = Wo % AA_RUN == 0 && ((uintptr_t)dst & 15) == 0;
+  const dim3 g1((unsigned)n1), g2((unsigned)n2), blk(256);
+  if (is_u8) {
+    if (v1) hipLaunchKernelGGL((k_imresize_aa_rows<true, true>), g1, blk, 0, st, src, tmp, B, H, W, Ho, scale, P);
+    else hipLaunchKernelGGL((k_imresize_aa_rows<true, false>), g1, blk, 0, st, src, tmp, B, H, W, Ho, scale, P);
+  } else {
+    if (v1) hipLaunchKernelGGL((k_imresize_aa_rows<false, true>), g1, blk, 0, st, src, tmp, B, H, W, Ho, scale, P);
+    else hipLaunchKernelGGL((k_imresize_aa_rows<false, false>), g1, blk, 0, st, src, tmp, B, H, W, Ho, scale, P);
+  }
+  if (v2) hipLaunchKernelGGL(k_imresize_aa_cols<true>, g2, blk, 0, st, (const float*)tmp, dst, (long)B * Ho, W, Wo, scale, P);
+  else hipLaunchKernelGGL(k_imresize_aa_cols<false>, g2, blk, 0, st, (const float*)tmp, dst, (long)B * Ho, W, Wo, scale, P);
+  SR_LAUNCH_CHECK("imresize_aa");
   return 0;
 }
 

@@ -121,7 +121,7 @@ def EvalPairsLike(args, pairs_h, pairs_l):
 
 
 class ResidentTrainSet:
-    """Training batches assembled ON the GPU from tiles that stay resident in HBM as uint8 (a CACO-2
+    """Training batches assembled ON the GPU from tiles that stay resident in HBM (uint8; float32 LR tiles of HR-only pairs) (a CACO-2
     split is a few hundred 8-bit tiles: tens of MB against 288 GB) -- the MI355X form of the TRAIN phase of
     DatasetDPSR.__getitem__ + DataLoader (dataset_dpsr.py:746-757,826-947, utils_dataloaders.py:138-158) for
     sets that ship true low-resolution tiles:
@@ -137,6 +137,11 @@ class ResidentTrainSet:
     --ppiw, h_per_pixel_weight.  Also from the reference's item (round 3):
       * pairs without a true LR tile (or --use_interpolated_low): the LR tile is synthesised once at construction as the
         reference does per item (:776-804; dlib/datasets/lowres.py, seeded by the item index);
+      * HR-only pairs -- no true LR tile and not a CACO-2 tile, e.g. the BioSR folds (:798-824,862-867): the LR tile is
+        util.imresize_np of the mod-cropped HR tile / 255, computed once at construction by srhip_imresize_aa and kept
+        resident in FLOAT32 (neither quantised nor clipped); its patches come from srhip_patch_gather_f32.  The reference
+        crops such pairs uniformly and asserts it (:863-864); so does the constructor.  One set may mix uint8 and float
+        LR tiles (CACO-2 and HR-only folds in one --train_dsets list);
       * the ROI image of the samplers is the LR tile brought to the HR size by srhip_resize_cubic (cv2.resize, :813-821);
         'edt' / 'edt*roi' and the Otsu threshold draw on the host through PatchSampler (scipy), 'roi' + fixed threshold
         on the device;
@@ -167,16 +172,25 @@ class ResidentTrainSet:
             self.host_sampler = PatchSampler(style, self.psize, int(getattr(args, 'color_max', 255)) + 1, th_style,
                                              float(getattr(args, 'sample_tr_patch_th', 0) or 0))
         ev = EvalPairsLike(args, pairs_h, pairs_l)
+        self.hr_only = [ev.is_hr_only(idx) for idx in range(len(self.ids_h))]
+        if any(self.hr_only) and style != SAMPLE_UNIF:
+            # dataset_dpsr.py:863-864: `spatch = self.args.sample_tr_patch; assert spatch == constants.SAMPLE_UNIF, spatch`
+            raise AssertionError(f"{style} (sample_tr_patch: a pair whose low-resolution image is synthesised from a tile "
+                                 f"that is not a CACO-2 tile is cropped uniformly only; first: "
+                                 f"{self.ids_h[self.hr_only.index(True)]})")
         hr_host = []
         for idx, (hk, lk) in enumerate(zip(self.ids_h, self.ids_l)):
             h_path = pairs_h[hk]['abs_path']
             h_full = imread_gray_uint8(h_path)
-            l_np, _ = ev.low_res_u8(idx, h_full, h_path)                  # true tile, or the reference's synthesis
             h = torch.from_numpy(h_full[:, :, 0].copy())
-            l = torch.from_numpy(np.array(l_np[:, :, 0], copy=True))
             hh, ww = h.shape[0] - h.shape[0] % self.sf, h.shape[1] - h.shape[1] % self.sf      # modcrop
             h = h[:hh, :ww].contiguous()
-            l = l[:hh // self.sf, :ww // self.sf].contiguous()
+            if self.hr_only[idx]:                                         # float32, resident: imresize_np of the cropped tile
+                l = ev.low_res_f32(h_full[:hh, :ww], self.device).contiguous()
+            else:
+                l_np, _ = ev.low_res_u8(idx, h_full, h_path)              # true tile, or the reference's synthesis
+                l = torch.from_numpy(np.array(l_np[:, :, 0], copy=True))
+                l = l[:hh // self.sf, :ww // self.sf].contiguous()
             assert l.shape == (hh // self.sf, ww // self.sf), (hk, tuple(h.shape), tuple(l.shape))
             assert hh >= self.psize and ww >= self.psize, f"{hk}: tile {hh}x{ww} < patch {self.psize}"
             self.hr.append(h.to(self.device))

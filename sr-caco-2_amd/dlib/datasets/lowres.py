@@ -10,6 +10,8 @@ hundred pixels, with the reference's own random-number streams so that a seeded 
   da_blur / da_dot_bin_noise / da_add_gaus_noise   :1071-1180   the LR-only augmentations on a random block
   otsu_threshold                     skimage.filters.threshold_otsu on a uint8 image (the 'automatic_threshold' ROI style;
                                       skimage is not in this image: restated, parity unpinned)
+  (the LR image of an HR-only pair -- :798-824, util.imresize_np -- is dlib.utils.utils_image.imresize_np on the host and
+   srhip_imresize_aa on the device; it stays float32: EvalPairs.low_res_f32, ResidentTrainSet)
 Device functions (libsrhip):
   l_to_h                  :659-683   cv2.resize(INTER_CUBIC) of the LR image to the HR size: srhip_resize_cubic
   per_pixel_weight        :1037-1056 weight image of an HR patch: a lookup of the per-colour table

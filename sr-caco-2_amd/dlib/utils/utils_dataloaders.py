@@ -129,9 +129,16 @@ class EvalPairs:
     with l_im / h_im / l_to_h_img float32 CHW in [0,1] = uint8 / 255 (utils_image.py:322-323,381-382).
 
     True low-resolution tiles are read; where a pair has none (or --use_interpolated_low) the LR input is synthesised as
-    the reference does for CACO-2 tiles (:776-804: bicubic down-scaling of the HR tile + seeded noise in the cells'
-    region; dlib/datasets/lowres.py).  'l_to_h_img' -- the LR image brought to the HR size by cv2.resize(INTER_CUBIC),
-    what the SRCNN-style nets consume (model_plain.py:184-195) -- comes from srhip_resize_cubic on the device."""
+    the reference does: for CACO-2 tiles (:776-804) bicubic down-scaling of the HR tile + seeded noise in the cells'
+    region (dlib/datasets/lowres.py); for every other set -- an HR-only set such as the BioSR folds -- (:798-824)
+    ``util.imresize_np(img_h, 1 / sf, True)`` of the MOD-CROPPED HR tile / 255, the MATLAB-style antialiased bicubic
+    down-scaling (srhip_imresize_aa on the device, dlib.utils.utils_image.imresize_np without one).  That image stays
+    float32 -- neither quantised nor clipped -- and l_path = h_path.  'l_to_h_img' -- the LR image brought to the HR size
+    by cv2.resize(INTER_CUBIC), what the SRCNN-style nets consume (model_plain.py:184-195) -- comes from
+    srhip_resize_cubic on the device; for an HR-only pair its source is uint8(trunc(clamp(l_im * color_max, 0, 255))).  The
+    reference truncates with ``astype(np.uint8)`` WITHOUT the clamp (:817): outside [0, 255] that conversion wraps or is
+    undefined (a sharp 0/1 edge down-scaled by 2 reaches -0.04 .. 1.07), so this build clamps first; inside the range the
+    two agree."""
 
     def __init__(self, args, pairs_h: dict, pairs_l: dict):
         self.args, self.pairs_h, self.pairs_l = args, pairs_h, pairs_l
@@ -144,18 +151,43 @@ class EvalPairs:
     def __len__(self):
         return len(self.im_h_ids)
 
-    def low_res_u8(self, index: int, img_h: np.ndarray, h_path: str):
-        """(LR tile uint8 HWC, its path): the true tile, or the reference's synthesis (:776-804)."""
-        from dlib.datasets import lowres
-        h_id = self.im_h_ids[index]
-        l_id = self.pairs_h[h_id]['low_path_key']
+    def _true_low_path(self, index: int):
+        """path of the pair's true LR tile, or None when the LR image is synthesised (:783-786)"""
+        l_id = self.pairs_h[self.im_h_ids[index]]['low_path_key']
         l_path = self.pairs_l[l_id]['abs_path'] if (self.pairs_l and l_id in self.pairs_l) else ''
         synth = (not os.path.isfile(l_path)) or bool(getattr(self.args, 'use_interpolated_low', False))
-        if not synth:
+        return None if synth else l_path
+
+    def is_hr_only(self, index: int) -> bool:
+        """The pair's LR image is synthesised and its HR tile is not a CACO-2 tile: the LR image is the antialiased bicubic
+        down-scaling of the HR tile, kept in float32 (:798-824)."""
+        from dlib.datasets import lowres
+        h_path = self.pairs_h[self.im_h_ids[index]]['abs_path']
+        return self._true_low_path(index) is None and not lowres.is_caco2(h_path)
+
+    def low_res_f32(self, img_h: np.ndarray, device=None):
+        """util.imresize_np(uint2single(img_h), 1 / sf, True) of a MOD-CROPPED HR tile (uint8 HxWx1), float32 and neither
+        quantised nor clipped: a [h, w] tensor on ``device`` from srhip_imresize_aa, or -- device None -- an hxwx1 numpy
+        array from the host function (the path of a machine without a GPU)."""
+        assert img_h.dtype == np.uint8 and img_h.ndim == 3 and img_h.shape[2] == 1, (img_h.dtype, img_h.shape)
+        if device is None:
+            from dlib.utils.utils_image import imresize_np
+            return imresize_np(np.float32(img_h / 255.), 1 / self.sf, True)
+        import torch
+        from srhip import ops
+        tile = torch.from_numpy(np.array(img_h[:, :, 0], copy=True))[None].to(device)
+        return ops.imresize_aa(tile, 1 / self.sf)[0]
+
+    def low_res_u8(self, index: int, img_h: np.ndarray, h_path: str):
+        """(LR tile uint8 HWC, its path): the true tile, or the reference's synthesis for a CACO-2 tile (:776-804).  The
+        pairs of an HR-only set (is_hr_only) have a float LR image: low_res_f32."""
+        from dlib.datasets import lowres
+        h_id = self.im_h_ids[index]
+        l_path = self._true_low_path(index)
+        if l_path is not None:
             return imread_gray_uint8(l_path), l_path
         if not lowres.is_caco2(h_path):
-            raise NotImplementedError(f'{h_id}: synthesised low-resolution inputs are built for CACO-2 tiles (dataset_dpsr.py:'
-                                      f'789-799; other sets go through utils_image.imresize_np, outside this build)')
+            raise ValueError(f'{h_id}: the low-resolution image of an HR-only pair is float32 (low_res_f32), not a uint8 tile')
         cmin, cmax = getattr(self.args, 'color_min', 0), getattr(self.args, 'color_max', 255)
         lo = lowres.interpolate_torch(img_h, 1. / self.sf, getattr(self.args, 'basic_interpolation', 'bicubic'), cmin, cmax)
         lo = np.clip(lo, a_min=cmin, a_max=cmax)
@@ -170,14 +202,28 @@ class EvalPairs:
         l_id = self.pairs_h[h_id]['low_path_key']
         h_path = self.pairs_h[h_id]['abs_path']
         img_h_full = imread_gray_uint8(h_path)
-        img_l, l_path = self.low_res_u8(index, img_h_full, h_path)      # the synthesis sees the un-cropped tile (:752-760)
         hh, ww = img_h_full.shape[:2]
         img_h = img_h_full[:hh - hh % self.sf, :ww - ww % self.sf]            # modcrop (utils_image.py:295-306)
         to_t = lambda a: torch.from_numpy(np.ascontiguousarray(np.float32(a / 255.))).permute(2, 0, 1).float()
-        out = {'l_im': to_t(img_l), 'l_id': l_id, 'l_path': l_path, 'h_im': to_t(img_h), 'h_id': h_id, 'h_path': h_path}
-        if torch.cuda.is_available():
+        gpu = torch.cuda.is_available()
+        if self.is_hr_only(index):                   # imresize_np of the mod-cropped tile, kept in float32 (:777,810-813)
+            if gpu:
+                l_dev = self.low_res_f32(img_h, 'cuda')
+                l_t = l_dev[None].cpu()
+                cmax = getattr(self.args, 'color_max', None)
+                cmax = 255. if cmax is None else float(cmax)
+                lu8 = (l_dev * cmax).clamp_(0., 255.).to(torch.uint8)[None]     # (img_l * color_max).astype(np.uint8) (:817)
+            else:
+                l_t = torch.from_numpy(self.low_res_f32(img_h)).permute(2, 0, 1).contiguous()
+            l_path = h_path
+        else:
+            img_l, l_path = self.low_res_u8(index, img_h_full, h_path)  # the synthesis sees the un-cropped tile (:752-760)
+            l_t = to_t(img_l)
+            if gpu:
+                lu8 = torch.from_numpy(np.array(img_l[:, :, 0], copy=True))[None].cuda()
+        out = {'l_im': l_t, 'l_id': l_id, 'l_path': l_path, 'h_im': to_t(img_h), 'h_id': h_id, 'h_path': h_path}
+        if gpu:
             from srhip import ops
-            lu8 = torch.from_numpy(np.array(img_l[:, :, 0], copy=True))[None].cuda()
             up = lowres.l_to_h(lu8, img_h.shape[:2])                     # cv2.resize(img_l, (W, H), INTER_CUBIC) (:813-821,836)
             out['l_to_h_img'] = ops.u8_to_unit(up)                       # [1, H, W] float32 on the device
             out['l_to_h_img_aug'] = out['l_to_h_img']

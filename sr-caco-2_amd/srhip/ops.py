@@ -1801,6 +1801,50 @@ def patch_gather(tiles, ids, y0, x0, modes, P, out=None):
     return out
 
 
+class _PatchJobF32(ctypes.Structure):   # srhip_patch_job_f32 (include/srhip.h)
+    _fields_ = [("img", ctypes.c_void_p), ("H", ctypes.c_int), ("W", ctypes.c_int), ("y0", ctypes.c_int),
+                ("x0", ctypes.c_int), ("mode", ctypes.c_int)]
+
+
+def patch_gather_f32(tiles, ids, y0, x0, modes, P, out=None):
+    """patch_gather out of device-resident FLOAT32 tiles (the low-resolution tiles of HR-only pairs, which stay the
+    float image of util.imresize_np: dataset_dpsr.py:810,872-873,893): the same crop / augment_img mode / [B,1,P,P]
+    layout, a pure copy."""
+    B = len(ids)
+    dev = tiles[ids[0]].device
+    if out is None:
+        out = torch.empty(B, 1, P, P, device=dev, dtype=torch.float32)
+    _chk(out)
+    jobs = (_PatchJobF32 * B)()
+    for b in range(B):
+        t = tiles[ids[b]]
+        if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous()):
+            raise ValueError("patch_gather_f32: tiles must be contiguous float32 CUDA tensors [H, W]")
+        jobs[b].img, jobs[b].H, jobs[b].W = t.data_ptr(), t.shape[0], t.shape[1]
+        jobs[b].y0, jobs[b].x0, jobs[b].mode = int(y0[b]), int(x0[b]), int(modes[b])
+    call("srhip_patch_gather_f32", ctypes.addressof(jobs), B, P, _p(out), _st())
+    return out
+
+
+def imresize_aa(src, scale, out=None):
+    """util.imresize_np(img, scale, antialiasing=True) for scale < 1 on a batch of 1-channel images [B, H, W], uint8 (read
+    as v / 255) or float32 -> float32 [B, ceil(H * scale), ceil(W * scale)]: the MATLAB-style antialiased bicubic
+    down-scaling behind the low-resolution image of an HR-only pair (resize.hip; utils_image.py:1358-1422,1505-1578)."""
+    if not src.is_cuda:
+        raise SrhipError("srhip ops need CUDA/HIP tensors (no CPU fallback exists)")
+    assert src.dim() == 3 and src.is_contiguous() and src.dtype in (torch.uint8, torch.float32), (src.shape, src.dtype)
+    import math
+    B, H, W = src.shape
+    scale = float(scale)
+    Ho, Wo = math.ceil(H * scale), math.ceil(W * scale)
+    if out is None:
+        out = torch.empty(B, Ho, Wo, device=src.device, dtype=torch.float32)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, Ho, Wo), out.shape
+    tmp = SCRATCH.get("imresize_aa_rows", B * Ho * W, torch.float32, src.device)
+    call("srhip_imresize_aa", _p(src), int(src.dtype == torch.uint8), _p(tmp), _p(out), B, H, W, Ho, Wo, scale, _st())
+    return out
+
+
 def resize_cubic(src, size_hw, out=None):
     """cv2.resize(src, (w, h), interpolation=cv2.INTER_CUBIC) on a batch of 1-channel images [B, H, W] (uint8 or float32)
     -> [B, h, w] of the same dtype (resize.hip; dataset_dpsr.py:659-683)."""
@@ -1904,10 +1948,22 @@ def roi_sample(tiles, ids, P, threshold, uniforms):
 def train_batch(hr_tiles, lr_tiles, ids, y0, x0, modes, patch_size, sf):
     """The batch dict the reference's trainer feeds ModelPlain (keys l_im, h_im; dataset_dpsr.py:981-1005)
     from resident tiles: HR crop at (y0, x0), LR crop at (y0 // sf, x0 // sf) of size patch_size // sf,
-    the same augmentation mode on both (dataset_dpsr.py:866-894)."""
-    return {"h_im": patch_gather(hr_tiles, ids, y0, x0, modes, patch_size),
-            "l_im": patch_gather(lr_tiles, ids, [v // sf for v in y0], [v // sf for v in x0], modes,
-                                 patch_size // sf)}
+    the same augmentation mode on both (dataset_dpsr.py:866-894).  An LR tile is uint8 (a true or CACO-2-synthesised
+    tile) or float32 (the antialiased down-scaling of an HR-only pair, imresize_aa); one batch may hold both."""
+    ly, lx, lp = [v // sf for v in y0], [v // sf for v in x0], patch_size // sf
+    B = len(ids)
+    f32 = [lr_tiles[i].dtype == torch.float32 for i in ids]
+    if not any(f32):
+        l_im = patch_gather(lr_tiles, ids, ly, lx, modes, lp)
+    elif all(f32):
+        l_im = patch_gather_f32(lr_tiles, ids, ly, lx, modes, lp)
+    else:                         # a mixed batch: each gather fills its own samples
+        l_im = torch.empty(B, 1, lp, lp, device=lr_tiles[ids[0]].device, dtype=torch.float32)
+        for want, gather in ((False, patch_gather), (True, patch_gather_f32)):
+            sel = [b for b in range(B) if f32[b] == want]
+            pick = lambda v: [v[b] for b in sel]
+            l_im[sel] = gather(lr_tiles, pick(ids), pick(ly), pick(lx), pick(modes), lp)
+    return {"h_im": patch_gather(hr_tiles, ids, y0, x0, modes, patch_size), "l_im": l_im}
 
 
 # ------------------------------------------------------------------ metrics
