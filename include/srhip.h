@@ -948,6 +948,17 @@ int srhip_leaky_relu_mask(float* g, const float* a, long n, float alpha, void* s
 int srhip_nearest_up2_nhwc(float* lo, float* hi, int B, int h, int w, int C, int adjoint, void* stream);
 /* x[i] = x[i] > 0 ? x[i] : alpha * x[i] in place (nn.LeakyReLU(0.2) behind the 1-channel edge conv, network_mslapsr.py:80-83). */
 int srhip_leaky_relu(float* x, long n, float alpha, void* stream);
+/* nn.Dropout(p) with a counter-based mask (ACT's --ACT_dropout_rate: network_act.py:136-204), forward and backward:
+ *   out[i] = keep(offset + i) ? x[i] * scale : 0,   out may be x.
+ * keep(e) is output word e % 4 of Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85,
+ * ten rounds) of counter (low, high 32 bits of e / 4, site, 0) under key (low, high 32 bits of *seed) compared with thr:
+ * keep iff word >= thr.  The caller passes thr = round(p 2^32) and scale = 1 / (1 - p) for 0 <= p < 1; p >= 1 (a scale that
+ * is not finite, or below 1) is an error.  A mask depends on (*seed, site, element index) alone: the same call on the
+ * incoming gradient is the backward and nothing is kept in between; `offset` (a multiple of 4) is the index of x[0] in the
+ * whole tensor when the caller walks it in slices.  seed is a DEVICE pointer, read when the kernel runs: a launch captured
+ * in a hipGraph replays with the seed of that moment.  tests/philox_ref.py restates keep() in numpy. */
+int srhip_dropout(const float* x, float* out, long n, long offset, const long long* seed, int site, unsigned int thr,
+                  float scale, void* stream);
 /* out[0] = sum(x) (fp64 accumulation); workspace: 2048 doubles. */
 int srhip_sum(const float* x, long n, float* out, double* workspace, void* stream);
 

@@ -18,7 +18,7 @@ int sr_fail(int code, const char* fmt, ...) {
 extern "C" {
 
 const char* srhip_last_error(void) { return g_err; }
-int srhip_abi_version(void) { return 13; }
+int srhip_abi_version(void) { return 14; }
 int srhip_experiments_enabled(void) {
 #ifdef SRHIP_EXPERIMENTS
   return 1;

@@ -3,7 +3,9 @@
 ``head.{0,1,2}``, ``linear_encoding``, ``mhsa_block.{i}.{0,1}``, ``csta_block.{i}.{0..4}``, ``cnn_branch.{g}.body.{r}`` and the
 unused ``cnn_branch.4`` conv, ``fusion_block / fusion_mlp / fusion_cnn``, ``conv_last``, ``tail``): released weights load with
 strict=True.  The compute is ``srhip.act_engine.ACTEngine``.  Training through the tape graph of the engine; 1-channel inputs; images of
-at least 6 x 6 pixels; GPU only."""
+at least 6 x 6 pixels; GPU only.  ``dropout_rate`` (--ACT_dropout_rate): the seven ``nn.Dropout`` of every fusion block, active in
+training mode only, with masks from the library's counter-based generator (srhip_dropout) under one seed tensor per forward
+(``sample_drop_path``)."""
 import math
 
 import torch
@@ -49,24 +51,24 @@ class _PreNorm2(nn.Module):
 
 
 class _FeedForward(nn.Module):                                    # :136-148
-    def __init__(self, dim, mlp_dim):
+    def __init__(self, dim, mlp_dim, dropout=0.0):
         super().__init__()
-        self.net = nn.Sequential(nn.Linear(dim, mlp_dim), nn.GELU(), nn.Dropout(0.0), nn.Linear(mlp_dim, dim), nn.Dropout(0.0))
+        self.net = nn.Sequential(nn.Linear(dim, mlp_dim), nn.GELU(), nn.Dropout(dropout), nn.Linear(mlp_dim, dim), nn.Dropout(dropout))
 
 
 class _SelfAttention(nn.Module):                                  # :151-183
-    def __init__(self, dim, heads, dim_head):
+    def __init__(self, dim, heads, dim_head, dropout=0.0):
         super().__init__()
         self.to_qkv = nn.Linear(dim, dim_head * heads * 3, bias=False)
-        self.to_out = nn.Sequential(nn.Linear(dim_head * heads, dim), nn.Dropout(0.0))
+        self.to_out = nn.Sequential(nn.Linear(dim_head * heads, dim), nn.Dropout(dropout))
 
 
 class _CrossAttention(nn.Module):                                 # :186-227
-    def __init__(self, dim, heads, dim_head):
+    def __init__(self, dim, heads, dim_head, dropout=0.0):
         super().__init__()
         self.to_q = nn.Linear(dim, dim_head * heads, bias=False)
         self.to_kv = nn.Linear(dim, dim_head * heads * 2, bias=False)
-        self.to_out = nn.Sequential(nn.Linear(dim_head * heads, dim), nn.Dropout(0.0))
+        self.to_out = nn.Sequential(nn.Linear(dim_head * heads, dim), nn.Dropout(dropout))
 
 
 class _CALayer(nn.Module):                                        # :230-247
@@ -101,13 +103,14 @@ class ACT(TapeNet):
         super().__init__()
         if upscale & (upscale - 1) or upscale < 2:
             raise NotImplementedError(f"ACT on libsrhip: power-of-two scales (got {upscale})")
-        if dropout_rate != 0.0:
-            raise NotImplementedError("ACT on libsrhip: dropout_rate 0 (evaluation)")
+        if not 0.0 <= dropout_rate < 1.0:
+            raise ValueError(f"ACT: 0 <= dropout_rate < 1 (got {dropout_rate})")
         if n_resgroups < n_fusionblocks or n_layers // 2 < n_fusionblocks:
             raise ValueError("ACT: n_resgroups and n_layers // 2 must cover n_fusionblocks (network_act.py:477-516)")
         self._init_protocol(upscale, in_chans)
         self.n_feats, self.n_resblocks, self.n_heads = n_feats, n_resblocks, n_heads
         self.token_size, self.n_fusionblocks = token_size, n_fusionblocks
+        self.dropout_rate = dr = float(dropout_rate)
         emb = n_feats * token_size ** 2
         self.embedding_dim = emb
         hidden = emb * expansion_ratio
@@ -118,15 +121,15 @@ class ACT(TapeNet):
         self.head = nn.Sequential(_conv(in_chans, n_feats, 3), _ResBlock(n_feats, 5), _ResBlock(n_feats, 5))
         self.linear_encoding = nn.Linear(emb, emb)
         self.mhsa_block = nn.ModuleList([
-            nn.ModuleList([_PreNorm(emb, _SelfAttention(emb, n_heads, dh)), _PreNorm(emb, _FeedForward(emb, hidden))])
+            nn.ModuleList([_PreNorm(emb, _SelfAttention(emb, n_heads, dh, dr)), _PreNorm(emb, _FeedForward(emb, hidden, dr))])
             for _ in range(n_layers // 2)])
         self.csta_block = nn.ModuleList([
             nn.ModuleList([
                 nn.Sequential(nn.LayerNorm(emb * 2), nn.Linear(emb * 2, emb // 2), nn.GELU(), nn.Linear(emb // 2, emb // 2)),
-                _PreNorm2(emb // 2, _CrossAttention(emb // 2, n_heads // 2, dh)),
-                _PreNorm2(emb // 2, _CrossAttention(emb // 2, n_heads // 2, dh)),
+                _PreNorm2(emb // 2, _CrossAttention(emb // 2, n_heads // 2, dh, dr)),
+                _PreNorm2(emb // 2, _CrossAttention(emb // 2, n_heads // 2, dh, dr)),
                 nn.Sequential(nn.LayerNorm(emb // 2), nn.Linear(emb // 2, emb // 2), nn.GELU(), nn.Linear(emb // 2, emb * 2)),
-                _PreNorm(emb, _FeedForward(emb, hidden)),
+                _PreNorm(emb, _FeedForward(emb, hidden, dr)),
             ]) for _ in range(n_layers // 2)])
         self.cnn_branch = nn.Sequential(*([_ResidualGroup(n_feats, reduction, n_resblocks) for _ in range(n_resgroups)]
                                           + [_conv(n_feats, n_feats, 3)]))
@@ -146,3 +149,11 @@ class ACT(TapeNet):
     def _make_engine(self):
         from srhip.act_engine import ACTEngine
         return ACTEngine(self)
+
+    def sample_drop_path(self, batch, device):
+        """The seed of this forward's dropout masks, or None where dropout is the identity (rate 0, evaluation mode): a one-
+        element int64 tensor drawn on the device by a generator op -- captured with a training step, it is drawn again at every
+        replay and follows torch.manual_seed.  The engine takes it as its `dp` argument."""
+        if self.dropout_rate == 0.0 or not self.training:
+            return None
+        return torch.randint(0, 2 ** 62, (1,), device=device)

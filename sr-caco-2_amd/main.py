@@ -202,7 +202,8 @@ def parse_input(argv=None):
                 constants.GRL: {'window_size': int, 'img_range': float, 'embed_dim': int, 'mlp_ratio': int},   # utils_parser.py:376-388
                 constants.OMNISR: {'num_feat': int, 'res_num': int, 'window_size': int, 'block_num': int},
                 constants.ACT: {'n_feats': int, 'n_resgroups': int, 'n_resblocks': int, 'reduction': int, 'n_heads': int,
-                                'n_layers': int, 'n_fusionblocks': int, 'token_size': int, 'expansion_ratio': int},
+                                'n_layers': int, 'dropout_rate': float, 'n_fusionblocks': int, 'token_size': int,
+                                'expansion_ratio': int},                                                       # utils_parser.py:362
                 constants.NLSN: {'n_resblocks': int, 'n_feats': int, 'n_hashes': int, 'chunk_size': int,
                                  'res_scale': float},
                 constants.SRFBN: {'num_features': int, 'num_steps': int, 'num_groups': int},
@@ -379,7 +380,9 @@ def main(argv=None):
             dist.destroy_process_group()
         return
     # no folds given: the same step on one synthetic batch of the configured shape (throughput / plumbing runs)
-    from dlib.utils.utils_config import clean_previous_checkpoints_except_last
+    from dlib.utils.utils_config import clean_previous_checkpoints_except_last, save_config
+    if args.is_master:
+        save_config(args, args.outd_backup, 'config_model.yml')                 # as a run over folds: what define_model reads back
     batch = synth_batch(args.batch_size, args.scale, args.h_size, model.device, 1000 + rank)
     n_save = args.train['checkpoint_save']
     t0, seen = time.perf_counter(), 0

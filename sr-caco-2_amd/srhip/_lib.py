@@ -11,14 +11,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SRHIP_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libsrhip.so")
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "srhip.h")
-_CT = {"p": ctypes.c_void_p, "l": ctypes.c_long, "i": ctypes.c_int,
+_CT = {"p": ctypes.c_void_p, "l": ctypes.c_long, "i": ctypes.c_int, "u": ctypes.c_uint,
        "f": ctypes.c_float, "d": ctypes.c_double}
 
 
 def parse_header(path=HEADER):
     """include/srhip.h is the single source of truth: returns
-    {name: (return_code, arg_codes)} with p pointer, l long, i int, f float,
-    d double, s const char*."""
+    {name: (return_code, arg_codes)} with p pointer, l long, i int, u unsigned int,
+    f float, d double, s const char*."""
     text = open(path).read()
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     protos = {}
@@ -31,7 +31,7 @@ def parse_header(path=HEADER):
                 if "*" in a:
                     codes += "p"
                 else:
-                    codes += {"long": "l", "int": "i", "float": "f", "double": "d"}[a.split()[0]]
+                    codes += {"long": "l", "int": "i", "unsigned": "u", "float": "f", "double": "d"}[a.split()[0]]
         protos[name] = ({"const char*": "s", "int": "i", "long": "l"}[ret], codes)
     return protos
 

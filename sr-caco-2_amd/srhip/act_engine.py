@@ -5,7 +5,10 @@ kernels, the 5 x 5 head convs as im2col (srhip_unfold) + GEMM, Linears on the sp
 (sample, head) products as two batched launches (srhip_gemm_nt_batched) around srhip_softmax_rows, F.unfold / F.fold as srhip_unfold / srhip_fold, RCAN's channel
 attention as srhip_channel_gate.  Training (save=True) runs the same graph on the tape of srhip/tape.py (_forward_tape): the
 backward of every op is derived there from kernels of this library (the attention products transposed, F.fold / F.unfold as
-each other's adjoints, srhip_layernorm_rows_bwd, srhip_softmax_rows_bwd)."""
+each other's adjoints, srhip_layernorm_rows_bwd, srhip_softmax_rows_bwd).  A net with dropout_rate > 0 in training mode runs the
+tape graph whether or not it records (nn.Dropout follows module.training, not the grad mode): Tape.dropout at the seven
+nn.Dropout of every fusion block, in the reference's call order (sites 0 .. 7 n_fusionblocks - 1), masks by srhip_dropout
+under the seed tensor `dp`."""
 import math
 
 import torch
@@ -153,9 +156,13 @@ class ACTEngine:
     def forward(self, x3, dp=None, save=False):
         if not self.prepared:
             self.prepare()
+        net = self.net
+        if net.dropout_rate > 0.0 and net.training:
+            if dp is None:          # the autograd path (TrainStep draws the seed itself)
+                dp = net.sample_drop_path(x3.shape[0], x3.device)
+            return self._forward_tape(x3, dp, save)
         if save:
             return self._forward_tape(x3)
-        net = self.net
         B, H, W = x3.shape
         dev = x3.device
         nf, ts, emb = net.n_feats, net.token_size, net.embedding_dim
@@ -262,11 +269,17 @@ class ACTEngine:
         return y.view(B, 1, y.shape[1], y.shape[2])
 
     # ------------------------------------------------------------------ training: the same graph on the tape
-    def _forward_tape(self, x3):
+    def _forward_tape(self, x3, seed=None, save=True):
         """forward() op for op with the tape recording (srhip/tape.py): 3 x 3 convs on the bank's planes, everything on
-        token rows (Linears, 1 x 1 convs, the attention products) on the exact-f32 GEMMs."""
+        token rows (Linears, 1 x 1 convs, the attention products) on the exact-f32 GEMMs.  seed: the dropout masks' seed
+        tensor (None: no dropout); save False: the same graph without the recording (a training-mode forward under no_grad)."""
         net = self.net
-        t = Tape(self.bufs, self.bank, True, x3.device)
+        t = Tape(self.bufs, self.bank, save, x3.device)
+        t.seed = seed
+        rate = net.dropout_rate
+
+        def drop(v):
+            return v if seed is None else t.dropout(v, rate)
         nm = {id(p): k for k, p in net.named_parameters()}
         N = lambda p: nm[id(p)]
         B, H, W = x3.shape
@@ -291,7 +304,7 @@ class ACTEngine:
             inner = net.n_heads * net.dim_head
             o = t.attend(t.cols(qkv, 0, inner), t.cols(qkv, inner, 2 * inner), t.cols(qkv, 2 * inner, 3 * inner), B, T, T,
                          net.n_heads, net.dim_head, net.dim_head ** -0.5)
-            return lin(o, blk.fn.to_out[0])
+            return drop(lin(o, blk.fn.to_out[0]))
 
         def cross_attention(blk, xq, xkv, Tq, Tk):
             heads = net.n_heads // 2
@@ -299,10 +312,10 @@ class ACTEngine:
             q = lin(ln(xq, blk.norm), blk.fn.to_q)
             kv = lin(ln(xkv, blk.norm2), blk.fn.to_kv)
             o = t.attend(q, t.cols(kv, 0, inner), t.cols(kv, inner, 2 * inner), B, Tq, Tk, heads, net.dim_head, net.dim_head ** -0.5)
-            return lin(o, blk.fn.to_out[0])
+            return drop(lin(o, blk.fn.to_out[0]))
 
         def ffn(blk, x):
-            return lin(t.unary(lin(ln(x, blk.norm), blk.fn.net[0]), "gelu"), blk.fn.net[3])
+            return drop(lin(drop(t.unary(lin(ln(x, blk.norm), blk.fn.net[0]), "gelu")), blk.fn.net[3]))
 
         def ln_mlp(seq, x):
             return lin(t.unary(lin(ln(x, seq[0]), seq[1]), "gelu"), seq[3])
@@ -367,7 +380,8 @@ class ACTEngine:
             parts = [t.conv(xv, f"tail.0.{2 * st}.{j}", (N(c.weight), N(c.bias), (j * F, (j + 1) * F))) for j in range(4)]
             xv = t.shuffle(t.cat_cols(parts), 2)
         out = t.conv_out1(xv, net.tail[1].weight, net.tail[1].bias, (N(net.tail[1].weight), N(net.tail[1].bias)))
-        self.saved = (t, out)
+        if save:
+            self.saved = (t, out)
         Bo, Ho, Wo = out.t.shape
         return out.t.view(Bo, 1, Ho, Wo)
 

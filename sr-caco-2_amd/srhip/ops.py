@@ -464,6 +464,22 @@ def unary_bwd(xy, g, out, kind):
     return out
 
 
+def dropout(x, out, seed, site, p, offset=0):
+    """nn.Dropout(p) in training mode with the library's counter-based masks (srhip_dropout: Philox4x32-10 of (seed, site,
+    element index)): out = keep ? x / (1 - p) : 0; out may be x.  seed: a one-element int64 CUDA tensor, read by the kernel;
+    offset: the index of x's first element in the whole tensor (a multiple of 4) when x is a slice of it.  The same call on
+    the gradient is the backward.  p outside [0, 1) is the library's error."""
+    _chk(x, out)
+    if not seed.is_cuda or seed.dtype != torch.int64 or seed.numel() != 1:
+        raise SrhipError("dropout: the seed is a one-element int64 CUDA/HIP tensor")
+    assert x.dtype == out.dtype == torch.float32 and x.is_contiguous() and out.is_contiguous() and x.numel() == out.numel()
+    p = float(p)
+    thr = min(max(int(round(p * 4294967296.0)), 0), 0xFFFFFFFF)
+    scale = 1.0 / (1.0 - p) if p < 1.0 else float("inf")
+    call("srhip_dropout", _p(x), _p(out), x.numel(), int(offset), _p(seed), int(site), thr, scale, _st())
+    return out
+
+
 def fft2_mag_pow_shift(x, out, gamma=0.8, eps=1e-8):
     """out = fftshift2d((|fftn(x, dim=(H, W))| + eps) ** gamma) on NHWC [B, H, W, C] (network_dfcan.py:27-36,60-64)."""
     _chk(x, out)

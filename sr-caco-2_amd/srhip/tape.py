@@ -287,6 +287,7 @@ class Tape:
         self.back = _BackList(self)          # (backward closure, values, buffers of its op), forward order
         self.tag = "t" if save else "e"
         self._gtmp = 0
+        self.seed, self._site = None, 0      # dropout: the step's seed tensor (the engine sets it) and the next site number
         self.pool = None
         if save:
             if getattr(bufs, "pool", None) is None:
@@ -707,6 +708,34 @@ class Tape:
                     return
                 g = out.g if out.g.is_contiguous() else out.g.contiguous()
                 self.acc(x, lambda o: ops.unary_bwd(xin if kind == "gelu" else y, g, o, kind))
+            self.back.append(bwd)
+        return out
+
+    def _dropout(self, x, out, site, p):
+        """one dropout site over a whole tensor, LIMIT elements per launch: every slice passes its element offset, so the
+        mask does not depend on the slicing"""
+        xf, of = x.view(-1), out.view(-1)
+        step = LIMIT & ~3
+        for o in range(0, xf.numel(), step):
+            ops.dropout(xf[o:o + step], of[o:o + step], self.seed, site, p, offset=o)
+
+    def dropout(self, x, p):
+        """nn.Dropout(p) in training mode: out = mask * x / (1 - p), the mask from the library's counter-based generator
+        (srhip_dropout) under the tape's seed tensor and this call's site number -- a counter the tape advances per call, in
+        forward order.  The backward applies the same launch to the gradient: the mask is regenerated, nothing is kept."""
+        assert self.seed is not None, "Tape.dropout: the tape has no seed tensor (Tape.seed)"
+        site = self._site
+        self._site += 1
+        xin = self._c(x.t)
+        y = self.new(*xin.shape)
+        self._dropout(xin, y, site, p)
+        out = self._out(y)
+        if self.save:
+            def bwd(x=x, out=out, site=site):
+                if out.g is None:
+                    return
+                g = self._c(out.g)
+                self.acc(x, lambda o: self._dropout(g, o, site, p))
             self.back.append(bwd)
         return out
 
