@@ -1,6 +1,8 @@
 /* libsrhip -- C-ABI of the MI355X (gfx950) hot path for SR-CACO-2 patch-level
  * super-resolution: 3x3 residual convolutions, pixel shuffle, SwinIR window
- * attention + MLP, L1/L2 losses, PSNR-family metrics, optimizers.
+ * attention + MLP, L1/L2 losses, PSNR-family metrics, optimizers, and the
+ * device side of the input pipeline (crops, crop samplers incl. the exact
+ * Euclidean distance transform, resizing).
  *
  * The reference (sbelharbi/sr-caco-2) has no FFI: its hot path is stock aten
  * calls made from Python.  Each entry point below
@@ -838,6 +840,40 @@ int srhip_im2col_c1(const float* x, float* out, long ldo, int B, int H, int W, i
 long srhip_roi_sample_ws(int B, int max_rows);
 int srhip_roi_sample(const srhip_patch_job* jobs, int B, int P, int threshold, const double* uniforms,
                      int* workspace, int max_rows, int* origins, void* stream);
+/* The 'edt' / 'edt*roi' styles and the per-tile Otsu threshold of the same sampler (dlib/datasets/dataset_dpsr.py:371-457,
+ * 479-480) on resident tiles.
+ * srhip_edt_sq: d2[H][W] = squared Euclidean distance of every pixel with img >= threshold to the nearest pixel with
+ * img < threshold, 0 on the latter -- in integers, so exact: scipy.ndimage.distance_transform_edt(img >= threshold) is its
+ * square root.  An image without any pixel below the threshold gets scipy's answer for that case, the distance to a virtual
+ * pixel at (-1, 0): (r + 1)^2 + c^2.  Sides above 16384 are refused (d2 < 2^31).  workspace: H * W ints, not d2. */
+int srhip_edt_sq(const unsigned char* img, int H, int W, int threshold, int* workspace, int* d2, void* stream);
+/* counts[256] = np.bincount(img, minlength=256) of n resident uint8 pixels (the call zeroes counts first): the histogram
+ * skimage's threshold_otsu works on (:479-480; the arithmetic on the counts is lowres.otsu_from_counts). */
+int srhip_hist_u8(const unsigned char* img, long n, int* counts, void* stream);
+/* Weighted patch origins.  Candidate (r, c) of the (H-P) x (W-P) origins looks at pixel (r + P/2, c + P/2); with
+ * roi = img >= threshold and d = sqrt(d2) there, its fp64 weight is
+ *   SRHIP_ORIGIN_ROI      exp(5 roi) + 1                       (:343-347; d2 may be NULL)
+ *   SRHIP_ORIGIN_EDT      d + 1                                (:389-392)
+ *   SRHIP_ORIGIN_EDTXROI  (exp(5 roi) + 1) (exp(d) + 1)        (:431-439)
+ * -- proportional to the probabilities the reference hands to np.random.multinomial.
+ * srhip_origin_rowcum fills tile->rowcum[H-P] (device) with the inclusive prefix of the candidate rows' total weights;
+ * rowcum[H-P-1] is the tile's grand total (not finite where exp(d) overflows: the reference's probabilities are NaN then).
+ * `tile` is a HOST struct.  srhip_origin_sample draws B origins: `table` is a DEVICE array of ntiles descriptors, each
+ * of which has passed srhip_origin_rowcum; ids[b] (device) names the tile of patch b, uniforms[b] in [0, 1) (device, fp64)
+ * selects the first candidate in row-major order whose cumulative weight exceeds uniforms[b] * total; origins[b] =
+ * {row, col} ({-1, -1} for an id outside the table).  No atomics: the same inputs give the same origins. */
+#define SRHIP_ORIGIN_ROI 0
+#define SRHIP_ORIGIN_EDT 1
+#define SRHIP_ORIGIN_EDTXROI 2
+typedef struct {
+  const unsigned char* img;   /* device pointer, [H][W] */
+  const int* d2;              /* device pointer, [H][W] (srhip_edt_sq) */
+  double* rowcum;             /* device pointer, [H - P] */
+  int H, W, threshold, P, style, pad_;
+} srhip_origin_tile;
+int srhip_origin_rowcum(const srhip_origin_tile* tile, void* stream);
+int srhip_origin_sample(const srhip_origin_tile* table, int ntiles, const int* ids, const double* uniforms, int B,
+                        int* origins, void* stream);
 
 /* ---- metrics (dlib/utils/utils_image.py:369-372,843-1007,618-653,1010-1198;
  *      dlib/utils/utils_trainer.py:961-1032) ----------------------------------- */

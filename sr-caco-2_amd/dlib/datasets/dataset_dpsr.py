@@ -13,8 +13,14 @@ published algorithm in dlib/datasets/lowres.py since skimage is not in this imag
 ``DeviceRoiSampler`` is the MI355X form of the 'roi' style: the tiles stay resident in HBM as
 uint8, one launch draws the origins of a whole batch from device-side uniforms by the inverse CDF of
 the SAME probabilities (srhip_roi_sample), and they go straight into srhip_patch_gather -- no
-host round trip per sample, so 8 GPUs x 8 patches per step are not host-bound."""
+host round trip per sample, so 8 GPUs x 8 patches per step are not host-bound.
+
+``DeviceWeightedSampler`` is the same for 'edt', 'edt*roi' and every style under 'automatic_threshold' (a threshold per
+tile): what depends only on the tile -- Otsu's threshold from a device histogram, the exact squared distance transform
+(srhip_edt_sq), the fp64 row prefix of the weights ``origin_weights`` states -- is computed once at construction, and a batch
+is one srhip_origin_sample launch."""
 import math
+import os
 import random
 
 import numpy as np
@@ -32,6 +38,37 @@ def roi_probabilities(img: np.ndarray, threshold: float, psize: int) -> np.ndarr
     roi = (img >= threshold).astype(np.float64)[lo:h - hi, lo:w - hi]
     wgt = np.exp(roi * 5.)
     return ((wgt.flatten() + 1.) / (wgt + 1.).sum()).reshape(roi.shape)
+
+
+def origin_weights(d2: np.ndarray, roi: np.ndarray, style: str) -> np.ndarray:
+    """Unnormalised fp64 weight of candidate origins, proportional to the reference's probabilities (:343-347,389-392,
+    431-439; its normalisers cancel): ``d2`` the SQUARED Euclidean distance to the nearest pixel outside the ROI and ``roi``
+    the ROI bit, both at the pixel the candidate looks at (row0 + P // 2, col0 + P // 2).  The formula srhip_origin_rowcum /
+    srhip_origin_sample evaluate on the device."""
+    assert style in (SAMPLE_ROI, SAMPLE_EDT, SAMPLE_EDTXROI), style
+    w_roi = np.exp(5. * np.asarray(roi, dtype=np.float64)) + 1.
+    if style == SAMPLE_ROI:
+        return w_roi
+    d = np.sqrt(np.asarray(d2, dtype=np.float64))
+    if style == SAMPLE_EDT:
+        return d + 1.
+    with np.errstate(over='ignore'):
+        return w_roi * (np.exp(d) + 1.)
+
+
+def check_origin_total(total: float, tile, style: str) -> float:
+    """The total weight of a tile must be finite: where exp(distance) overflows (distance above ~709) the reference's
+    probabilities are NaN and its np.random.multinomial raises; so does the construction of the device sampler."""
+    total = float(total)
+    if not math.isfinite(total) or total <= 0.:
+        raise ValueError(f"sample_tr_patch={style}: tile {tile}: the total origin weight is {total} (exp of the distance "
+                         f"transform overflows: the reference's probabilities are NaN for this tile)")
+    return total
+
+
+def int_threshold(th) -> int:
+    """for a uint8 image, img >= th with a float th is img >= ceil(th)"""
+    return int(math.ceil(float(th)))
 
 
 class PatchSampler(object):
@@ -114,6 +151,55 @@ class DeviceRoiSampler:
         return ops.roi_sample(self.tiles, ids, self.psize, self.threshold, u), u
 
 
+class DeviceWeightedSampler:
+    """'edt', 'edt*roi' and 'roi' sampling with one threshold PER TILE for a batch on the GPU (the styles and the
+    'automatic_threshold' of PatchSampler).  ``tiles``: resident uint8 CUDA tensors [H, W] as for DeviceRoiSampler;
+    ``thresholds``: one number for all tiles, a list with one per tile, or None = Otsu's threshold of each tile
+    (lowres.otsu_from_counts on srhip_hist_u8's counts).  Per tile and once: d2 = srhip_edt_sq (4 B per pixel, kept), the
+    fp64 row prefix of ``origin_weights`` and the total, which must be finite (check_origin_total names the tile
+    otherwise).  ``sample(ids)`` -> (int32 [B, 2] origins (row, col) on the device, the uniforms): one launch, the
+    inverse CDF in row-major order.
+
+    The probabilities are the reference's; the random stream is not: the host PatchSampler consumes numpy's global stream
+    through np.random.multinomial, this one a torch device generator seeded like DeviceRoiSampler's (myseed + rank), as
+    'roi' + 'fix_threshold' has done since round 2."""
+
+    def __init__(self, tiles, psize: int, style: str, thresholds=None, seed: int = 0, names=None):
+        import torch
+        from srhip import ops
+        from dlib.datasets.lowres import otsu_from_counts
+        assert style in (SAMPLE_ROI, SAMPLE_EDT, SAMPLE_EDTXROI), style
+        self.tiles, self.psize, self.style = tiles, int(psize), style
+        dev = tiles[0].device
+        if thresholds is None:
+            thresholds = [otsu_from_counts(ops.hist_u8(t).cpu().numpy()) for t in tiles]
+        elif not isinstance(thresholds, (list, tuple)):
+            thresholds = [thresholds] * len(tiles)
+        assert len(thresholds) == len(tiles), (len(thresholds), len(tiles))
+        self.thresholds = [int_threshold(t) for t in thresholds]
+        self.d2, self.rowcum, self.totals, desc = [], [], [], []
+        for k, (t, th) in enumerate(zip(tiles, self.thresholds)):
+            d2 = ops.edt_sq(t, th) if style != SAMPLE_ROI else None
+            d, rowcum = ops.origin_rowsums(t, d2, self.psize, th, style)
+            self.totals.append(check_origin_total(rowcum[-1].item(), names[k] if names else k, style))
+            self.d2.append(d2)
+            self.rowcum.append(rowcum)
+            desc.append(d)
+        self.table = ops.origin_table(desc, dev)          # built once: a launch takes tile ids and uniforms only
+        self.gen = torch.Generator(device=dev)
+        self.gen.manual_seed(int(seed))
+
+    def sample(self, ids):
+        import torch
+        from srhip import ops
+        dev = self.tiles[0].device
+        if not isinstance(ids, torch.Tensor):
+            assert all(0 <= i < len(self.tiles) for i in ids), ids
+            ids = torch.tensor(ids, dtype=torch.int32).to(dev)
+        u = torch.rand(ids.numel(), dtype=torch.float64, device=dev, generator=self.gen)
+        return ops.origin_sample(self.table, ids, u), u
+
+
 def EvalPairsLike(args, pairs_h, pairs_l):
     """the LR resolution logic (true tile or synthesis) is EvalPairs' (utils_dataloaders.py)"""
     from dlib.utils.utils_dataloaders import EvalPairs
@@ -143,8 +229,11 @@ class ResidentTrainSet:
         crops such pairs uniformly and asserts it (:863-864); so does the constructor.  One set may mix uint8 and float
         LR tiles (CACO-2 and HR-only folds in one --train_dsets list);
       * the ROI image of the samplers is the LR tile brought to the HR size by srhip_resize_cubic (cv2.resize, :813-821);
-        'edt' / 'edt*roi' and the Otsu threshold draw on the host through PatchSampler (scipy), 'roi' + fixed threshold
-        on the device;
+        every style draws on the device: 'roi' + fixed threshold through srhip_roi_sample (DeviceRoiSampler), 'edt' /
+        'edt*roi' and every style under 'automatic_threshold' (Otsu, per tile) through DeviceWeightedSampler -- the exact
+        distance transform, the thresholds and the fp64 row prefixes are computed once at construction, a batch is one
+        srhip_origin_sample launch.  SRHIP_HOST_SAMPLER=1 in the environment keeps these on the host PatchSampler (scipy
+        per sample), the baseline of tools/sampler_rate.py;
       * the LR-only augmentations (--da_blur / --da_dot_bin_noise / --da_add_gaus_noise, :899-905) run on the host on
         the B low-resolution patches (a few hundred pixels each) with the reference's numpy stream, then l_to_h_img is
         resized from the augmented patch on the device and clipped (:905-906);
@@ -168,7 +257,9 @@ class ResidentTrainSet:
         th_style = getattr(args, 'sample_tr_patch_th_style', TH_FIX)
         self.device_roi = style == SAMPLE_ROI and th_style == TH_FIX
         self.host_sampler = None
-        if style != SAMPLE_UNIF and not self.device_roi:
+        self.device_weighted = (style != SAMPLE_UNIF and not self.device_roi
+                                and os.environ.get('SRHIP_HOST_SAMPLER', '') != '1')
+        if style != SAMPLE_UNIF and not self.device_roi and not self.device_weighted:
             self.host_sampler = PatchSampler(style, self.psize, int(getattr(args, 'color_max', 255)) + 1, th_style,
                                              float(getattr(args, 'sample_tr_patch_th', 0) or 0))
         ev = EvalPairsLike(args, pairs_h, pairs_l)
@@ -201,6 +292,11 @@ class ResidentTrainSet:
         self.roi_host = [t.cpu().numpy() for t in self.roi_src] if self.host_sampler is not None else None
         if self.device_roi:
             self.roi = DeviceRoiSampler(self.roi_src, self.psize, int(args.sample_tr_patch_th), seed=int(args.myseed or 0) + rank)
+        if self.device_weighted:
+            self.weighted = DeviceWeightedSampler(
+                self.roi_src, self.psize, style,
+                thresholds=float(getattr(args, 'sample_tr_patch_th', 0) or 0) if th_style == TH_FIX else None,
+                seed=int(args.myseed or 0) + rank, names=self.ids_h)
         self.da = any(getattr(args, f, False) for f in ('da_blur', 'da_dot_bin_noise', 'da_add_gaus_noise'))
         self.ppiw_table = None
         if getattr(args, 'ppiw', False):
@@ -222,10 +318,10 @@ class ResidentTrainSet:
         P, sf = self.psize, self.sf
         for ids in self.sampler.batches(self.batch, drop_last=True):
             B = len(ids)
-            if self.device_roi:
-                org, _ = self.roi.sample(ids)
+            if self.device_roi or self.device_weighted:
+                org, _ = (self.roi if self.device_roi else self.weighted).sample(ids)
                 org = org.cpu().tolist()                      # B x 2 ints: the only host round trip of the batch
-            elif self.host_sampler is not None:               # 'edt' / 'edt*roi' / Otsu: the reference's sampler on the host
+            elif self.host_sampler is not None:               # SRHIP_HOST_SAMPLER=1: the reference's sampler on the host
                 org = [list(self.host_sampler(self.roi_host[i], False)[:2]) for i in ids]
             else:
                 u = torch.rand(B, 2, device=self.device, generator=self.gen).cpu()

@@ -10,6 +10,7 @@ hundred pixels, with the reference's own random-number streams so that a seeded 
   da_blur / da_dot_bin_noise / da_add_gaus_noise   :1071-1180   the LR-only augmentations on a random block
   otsu_threshold                     skimage.filters.threshold_otsu on a uint8 image (the 'automatic_threshold' ROI style;
                                       skimage is not in this image: restated, parity unpinned)
+  otsu_from_counts                   the same from a histogram (srhip_hist_u8's counts of a resident tile)
   (the LR image of an HR-only pair -- :798-824, util.imresize_np -- is dlib.utils.utils_image.imresize_np on the host and
    srhip_imresize_aa on the device; it stays float32: EvalPairs.low_res_f32, ResidentTrainSet)
 Device functions (libsrhip):
@@ -156,8 +157,21 @@ def otsu_threshold(img: np.ndarray, nbins: int = 256):
     lo, hi = int(flat.min()), int(flat.max())
     if lo == hi:
         return lo
-    counts = np.bincount(flat.astype(np.int64) - lo, minlength=hi - lo + 1).astype(np.float64)
-    centers = np.arange(lo, hi + 1).astype(np.float64)
+    return otsu_from_counts(np.bincount(flat.astype(np.int64) - lo, minlength=hi - lo + 1), first=lo)
+
+
+def otsu_from_counts(counts, first: int = 0):
+    """otsu_threshold from the image's histogram: counts[k] = number of pixels of grey level first + k (e.g. the 256 bins of
+    srhip_hist_u8 with first = 0).  Empty bins below the image's min and above its max are dropped, as skimage's histogram
+    of an integer image spans min..max only; a constant image returns its grey level."""
+    counts = np.asarray(counts)
+    nz = np.flatnonzero(counts)
+    assert nz.size, "otsu_from_counts: empty histogram"
+    lo, hi = int(nz[0]), int(nz[-1])
+    if lo == hi:
+        return first + lo
+    counts = counts[lo:hi + 1].astype(np.float64)
+    centers = np.arange(first + lo, first + hi + 1).astype(np.float64)
     w1 = np.cumsum(counts)
     w2 = np.cumsum(counts[::-1])[::-1]
     m1 = np.cumsum(counts * centers) / w1

@@ -1961,6 +1961,79 @@ def roi_sample(tiles, ids, P, threshold, uniforms):
     return out
 
 
+def _u8_tile(t, who):
+    if not (t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and t.is_contiguous()):
+        raise ValueError(f"{who}: the tile must be a contiguous uint8 CUDA tensor [H, W]")
+    return t
+
+
+def edt_sq(img, threshold, out=None):
+    """int32 [H, W]: the squared Euclidean distance of every pixel with img >= threshold to the nearest pixel below it (0
+    there) -- scipy.ndimage.distance_transform_edt(img >= threshold) ** 2, exact (edt.hip).  ``out``: an int32 CUDA buffer
+    of at least H * W elements, of which the first H * W are written."""
+    H, W = _u8_tile(img, "edt_sq").shape
+    if out is None:
+        out = torch.empty(H, W, dtype=torch.int32, device=img.device)
+    elif not (out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= H * W):
+        raise ValueError("edt_sq: out must be a contiguous int32 CUDA tensor of at least H * W elements")
+    ws = torch.empty(max(H * W, 1), dtype=torch.int32, device=img.device)      # once per tile, at construction: not SCRATCH
+    call("srhip_edt_sq", _p(img), H, W, int(threshold), _p(ws), _p(out), _st())
+    return out
+
+
+def hist_u8(img):
+    """int32 [256] on the device: np.bincount(img, minlength=256) of a resident uint8 image."""
+    if not (img.is_cuda and img.dtype == torch.uint8 and img.is_contiguous()):
+        raise ValueError("hist_u8: img must be a contiguous uint8 CUDA tensor")
+    counts = torch.empty(256, dtype=torch.int32, device=img.device)
+    call("srhip_hist_u8", _p(img), img.numel(), _p(counts), _st())
+    return counts
+
+
+class _OriginTile(ctypes.Structure):   # srhip_origin_tile (include/srhip.h)
+    _fields_ = [("img", ctypes.c_void_p), ("d2", ctypes.c_void_p), ("rowcum", ctypes.c_void_p), ("H", ctypes.c_int),
+                ("W", ctypes.c_int), ("threshold", ctypes.c_int), ("P", ctypes.c_int), ("style", ctypes.c_int),
+                ("pad_", ctypes.c_int)]
+
+
+ORIGIN_STYLES = {"roi": 0, "edt": 1, "edt*roi": 2}      # SRHIP_ORIGIN_*
+
+
+def origin_rowsums(img, d2, P, threshold, style):
+    """(descriptor, rowcum): rowcum float64 [H - P] on the device, the inclusive prefix of the candidate rows' total
+    weights under ``style`` ('roi' | 'edt' | 'edt*roi'; srhip.h: srhip_origin_rowcum); rowcum[-1] is the tile's total.
+    The descriptor is the tile's entry of the table origin_table() uploads."""
+    H, W = _u8_tile(img, "origin_rowsums").shape
+    if style != "roi" and not (d2 is not None and d2.is_cuda and d2.dtype == torch.int32 and d2.is_contiguous()
+                               and tuple(d2.shape) == (H, W)):
+        raise ValueError("origin_rowsums: d2 must be the int32 CUDA tensor [H, W] of edt_sq")
+    rowcum = torch.empty(max(H - int(P), 1), dtype=torch.float64, device=img.device)
+    t = _OriginTile(img.data_ptr(), None if style == "roi" else d2.data_ptr(), rowcum.data_ptr(), H, W, int(threshold),
+                    int(P), ORIGIN_STYLES[style], 0)
+    call("srhip_origin_rowcum", ctypes.addressof(t), _st())
+    return t, rowcum
+
+
+def origin_table(descriptors, device):
+    """The device table of origin_sample: the descriptors origin_rowsums returned, uploaded once."""
+    arr = (_OriginTile * len(descriptors))(*descriptors)
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+
+
+def origin_sample(table, ids, uniforms):
+    """Patch origins [B, 2] (row, col; int32, on the device) of the 'edt' / 'edt*roi' / per-tile-threshold 'roi' styles:
+    ``table`` from origin_table, ``ids`` an int32 CUDA tensor [B] of tile numbers, ``uniforms`` float64 [B] in [0, 1)."""
+    B = ids.numel()
+    if not (ids.is_cuda and ids.dtype == torch.int32 and ids.is_contiguous()):
+        raise ValueError("origin_sample: ids must be a contiguous int32 CUDA tensor")
+    if not (uniforms.is_cuda and uniforms.dtype == torch.float64 and uniforms.numel() == B and uniforms.is_contiguous()):
+        raise ValueError("origin_sample: uniforms must be a contiguous float64 CUDA tensor with one entry per patch")
+    out = torch.empty(B, 2, dtype=torch.int32, device=ids.device)
+    call("srhip_origin_sample", _p(table), table.numel() // ctypes.sizeof(_OriginTile), _p(ids), _p(uniforms), B, _p(out),
+         _st())
+    return out
+
+
 def train_batch(hr_tiles, lr_tiles, ids, y0, x0, modes, patch_size, sf):
     """The batch dict the reference's trainer feeds ModelPlain (keys l_im, h_im; dataset_dpsr.py:981-1005)
     from resident tiles: HR crop at (y0, x0), LR crop at (y0 // sf, x0 // sf) of size patch_size // sf,
