@@ -1018,6 +1018,41 @@ int srhip_bn_bwd(const float* dY, const float* A, const float* X, const float* c
                  const float* R, float* dgamma, float* dbeta, int accumulate, void* workspace, long workspace_bytes,
                  void* stream);
 
+/* ---- DSR-Splines (dsr_splines.hip): one spline net ("expert") per pixel.  The reference evaluates every spline over the
+ * whole interpolated image, masks each result by the spline's grey-level range and sums (DsrSplines.forward,
+ * dlib/models/network_dsr_splines.py:389-413; _SplineNet.forward / get_mask, :211-260); with one channel the masks partition
+ * the grey levels, so one expert owns a pixel, and behind the first in_ksz x in_ksz reflect-padded conv every layer is 1x1
+ * (_SplineNet._make_layers, :165-192; _Layer.forward, :84-93).
+ *   Network: n_hidden = 1 ... 8 hidden widths [32] * (n_hidden - 1) + [16] (constants.SPLINEHIDDEN), in_ksz odd, 1 ... 15.
+ *   Parameter table [n_splines][stride] floats: an expert's tensors in named_parameters() order -- per layer conv.weight,
+ *   conv.bias, then match_sz.weight, match_sz.bias where use_local_residual gives the layer a 1x1 conv (widths differ) -- each
+ *   padded to a multiple of 4 floats; srhip_dsr_splines_table_floats is an expert's size in that layout (-1: unsupported).
+ *   srhip_dsr_splines_pack copies n_splines * T separate tensors (device array of their pointers, expert-major) into the
+ *   table (to_table != 0) or back.
+ *   srhip_dsr_splines_order: expert_id[p] = level_to_expert[clamp(int(float32(x) * 255.0f), 0, 255)] (the reference's
+ *   (x * color_max).type(uint8), :223-226; level_to_expert: 256 device ints, the bins of np.array_split(range(256), n),
+ *   :343-348), order = the pixel positions sorted by expert, positions ascending within an expert (a stable counting sort,
+ *   no host read), meta = [257 segment offsets][257 first tiles][tile -> expert]; sizes from srhip_dsr_splines_order_sizes.
+ *   The launch grids depend on (pixels, n_splines) alone.
+ *   srhip_dsr_splines_fwd: y[p] = expert(p) (+ x_interp[p] under global_residual); x_interp, y [B][H][W].
+ *   srhip_dsr_splines_bwd: grad_table (same layout, stride grad_stride) = the parameter gradients for dy [B][H][W], summed in
+ *   a fixed order (bit-reproducible); every element of every expert is written, zeros for an expert that owns no pixel.
+ *   There is no input gradient (the bicubic interpolation takes none).  workspace: srhip_dsr_splines_bwd_ws() floats. */
+long srhip_dsr_splines_table_floats(int in_ksz, int n_hidden, int local_residual);
+int srhip_dsr_splines_pack(const long long* tensor_ptrs, float* table, long stride, int n_splines, int in_ksz, int n_hidden,
+                           int local_residual, int to_table, void* stream);
+int srhip_dsr_splines_order_sizes(long pixels, int n_splines, long* meta_ints, long* hist_ints);
+int srhip_dsr_splines_order(const float* x_interp, long pixels, const int* level_to_expert, int n_splines,
+                            unsigned char* expert_id, int* order, int* meta, int* hist, void* stream);
+int srhip_dsr_splines_fwd(const float* x_interp, const float* table, long stride, const int* order, const int* meta, float* y,
+                          int B, int H, int W, int n_splines, int in_ksz, int n_hidden, int local_residual,
+                          int global_residual, void* stream);
+long srhip_dsr_splines_bwd_ws(int n_splines, int in_ksz, int n_hidden, int local_residual);
+int srhip_dsr_splines_bwd(const float* x_interp, const float* dy, const float* table, long stride, const int* order,
+                          const int* meta, float* grad_table, long grad_stride, float* workspace, long workspace_floats,
+                          int B, int H, int W, int n_splines, int in_ksz, int n_hidden, int local_residual,
+                          int global_residual, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

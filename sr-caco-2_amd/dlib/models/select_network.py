@@ -97,6 +97,11 @@ def define_G(args):
                    level_compression=opt_net[f'{nt}_level_compression'], res_factor=opt_net[f'{nt}_res_factor'],
                    max_num_feature=opt_net[f'{nt}_max_num_feature'],
                    block_compression=opt_net[f'{nt}_block_compression'])
+    if net_type == constants.DSRSPLINES:            # select_network.py:212-223
+        from dlib.models.network_dsr_splines import DsrSplines as net
+        return net(**{k: opt_net[f'{nt}_{k}'] for k in ('upscale', 'in_planes', 'in_ksz', 'splinenet_type',
+                                                        'n_splines_per_color', 'use_local_residual', 'use_global_residual',
+                                                        'color_min', 'color_max')})
     raise NotImplementedError(
         f"net_type {net_type!r}: only {constants.MODELS} run on libsrhip (SURVEY.md section 8f lists "
         f"the remaining reference networks as 'next')")

@@ -19,7 +19,22 @@ DFCAN = 'DFCAN'  # https://www.nature.com/articles/s41592-020-01048-5 (reference
 ACT = 'ACT'  # https://arxiv.org/pdf/2203.07682.pdf (reference constants.py:37)
 OMNISR = 'OmniSR'  # https://arxiv.org/pdf/2304.10244.pdf (reference constants.py:34)
 GRL = 'GRL'  # https://arxiv.org/pdf/2303.00748.pdf (reference constants.py:35)
-MODELS = [SWINIR, EDSR_LIIF, VDSR, DRRN, SRCNN, MSLAPSR, MEMNET, DBPN, SRFBN, PROSR, ENLCN, NLSN, DFCAN, ACT, OMNISR, GRL]
+DSRSPLINES = 'DSR-Splines'  # the reference authors' own per-grey-level spline nets (reference constants.py:22)
+MODELS = [SWINIR, EDSR_LIIF, VDSR, DRRN, SRCNN, MSLAPSR, MEMNET, DBPN, SRFBN, PROSR, ENLCN, NLSN, DFCAN, ACT, OMNISR, GRL,
+          DSRSPLINES]
+
+# DSR-Splines: hidden widths of one spline net by type (reference constants.py:716-746)
+SPLINE_NET_TYPE1 = 'snet_type1'
+SPLINE_NET_TYPE2 = 'snet_type2'
+SPLINE_NET_TYPE3 = 'snet_type3'
+SPLINE_NET_TYPE4 = 'snet_type4'
+SPLINE_NET_TYPE5 = 'snet_type5'
+SPLINE_NET_TYPE6 = 'snet_type6'
+SPLINE_NET_TYPE7 = 'snet_type7'
+SPLINE_NET_TYPE8 = 'snet_type8'
+SPLINE_NET_TYPES = [SPLINE_NET_TYPE1, SPLINE_NET_TYPE2, SPLINE_NET_TYPE3, SPLINE_NET_TYPE4, SPLINE_NET_TYPE5,
+                    SPLINE_NET_TYPE6, SPLINE_NET_TYPE7, SPLINE_NET_TYPE8]
+SPLINEHIDDEN = {t: [32] * i + [16] for i, t in enumerate(SPLINE_NET_TYPES)}
 
 SWINIR_MTH = 'SWINIR'
 EDSR_LIIF_MTH = 'EDSR_LIIF'
@@ -37,7 +52,9 @@ DFCAN_MTH = 'DFCAN'
 ACT_MTH = 'ACT'
 OMNISR_MTH = 'OmniSR'
 GRL_MTH = 'GRL'
-NETTYPE_METHOD = {SWINIR: SWINIR_MTH, EDSR_LIIF: EDSR_LIIF_MTH, VDSR: VDSR_MTH, DRRN: DRRN_MTH, SRCNN: SRCNN_MTH,
+DSRSPLINES_MTH = 'DSR-SPLINES'
+NETTYPE_METHOD = {DSRSPLINES: DSRSPLINES_MTH,
+SWINIR: SWINIR_MTH, EDSR_LIIF: EDSR_LIIF_MTH, VDSR: VDSR_MTH, DRRN: DRRN_MTH, SRCNN: SRCNN_MTH,
                   MSLAPSR: MSLAPSR_MTH, MEMNET: MEMNET_MTH, DBPN: DBPN_MTH, SRFBN: SRFBN_MTH, PROSR: PROSR_MTH,
                   ENLCN: ENLCN_MTH, NLSN: NLSN_MTH, DFCAN: DFCAN_MTH, ACT: ACT_MTH,
                   OMNISR: OMNISR_MTH, GRL: GRL_MTH}

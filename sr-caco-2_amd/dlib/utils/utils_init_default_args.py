@@ -69,6 +69,11 @@ def init_net_g(netG: dict, args: dict) -> dict:
                     f'{nt}_upsampler': constants.US_PIXEL_SHUFFLE, f'{nt}_conv_type': '1conv', f'{nt}_out_proj_type': 'linear',
                     f'{nt}_anchor_window_down_factor': 2, f'{nt}_qkv_proj_type': 'linear', f'{nt}_anchor_proj_type': 'avgpool',
                     f'{nt}_local_connection': True})
+    elif netG['net_type'] == constants.DSRSPLINES:   # utils_init_default_args.py:258-270
+        out.update({f'{nt}_upscale': args['scale'], f'{nt}_in_planes': args['n_channels'], f'{nt}_color_min': 0,
+                    f'{nt}_color_max': 255, f'{nt}_in_ksz': 3, f'{nt}_splinenet_type': constants.SPLINE_NET_TYPE1,
+                    f'{nt}_n_splines_per_color': 16, f'{nt}_use_local_residual': False,
+                    f'{nt}_use_global_residual': False})
     else:
         raise NotImplementedError(netG['net_type'])
     out[f'{nt}_init_type'] = constants.INIT_W_DEFAULT

@@ -193,6 +193,8 @@ def parse_input(argv=None):
                                    'resi_connection': str, 'img_range': float},
                 constants.VDSR: {},
                 constants.SRCNN: {},
+                constants.DSRSPLINES: {'in_ksz': int, 'splinenet_type': str, 'n_splines_per_color': int,
+                                       'use_local_residual': str2bool, 'use_global_residual': str2bool},  # utils_parser.py:623-642
                 constants.MSLAPSR: {},
                 constants.MEMNET: {'num_memory_blocks': int, 'num_residual_blocks': int},
                 constants.DRRN: {'num_residual_units': int},

@@ -2203,3 +2203,81 @@ def bn_bwd(dy, x, coef, a=None, dx=None, res=None, dgamma=None, dbeta=None, accu
     call("srhip_bn_bwd", _p(dy), _p(a), _p(x), _p(coef), T, C, _p(dx), _p(res), _p(dgamma), _p(dbeta), int(bool(accumulate)),
          _p(ws), nb, _st())
     return dx
+
+
+# ------------------------------------------------------------------ DSR-Splines (dsr_splines.hip)
+def dsr_splines_level_table(n_splines, color_min=0, color_max=255):
+    """The 256-entry grey level -> expert table: the bins of np.array_split(range(color_min, color_max + 1), n)
+    (DsrSplines._make_splines, network_dsr_splines.py:343-348), uneven when n does not divide the count.  Host, int32."""
+    import numpy as np
+    assert (color_min, color_max) == (0, 255), "DSR-Splines (libsrhip): uint8 grey levels 0 ... 255"
+    lut = np.empty(256, dtype=np.int32)
+    for k, s in enumerate(np.array_split(np.arange(color_min, color_max + 1), n_splines)):
+        lut[s] = k
+    return torch.from_numpy(lut)
+
+
+def dsr_splines_table_floats(in_ksz, n_hidden, local):
+    """Floats of one expert in the parameter table (every tensor padded to a multiple of four)."""
+    n = lib.srhip_dsr_splines_table_floats(int(in_ksz), int(n_hidden), int(bool(local)))
+    if n < 0:
+        raise SrhipError(f"DSR-Splines: in_ksz {in_ksz} (odd, 1 ... 15) with {n_hidden} hidden widths (1 ... 8) is not supported")
+    return n
+
+
+def dsr_splines_pack(ptrs, table, n_splines, in_ksz, n_hidden, local, to_table=True):
+    """ptrs: int64 CUDA tensor of the n_splines * T tensor addresses (expert-major, named_parameters() order); one launch."""
+    assert ptrs.is_cuda and ptrs.dtype == torch.int64 and table.dim() == 2 and table.stride(1) == 1
+    _chk(table)
+    call("srhip_dsr_splines_pack", _p(ptrs), _p(table), table.stride(0), n_splines, in_ksz, n_hidden, int(bool(local)),
+         int(bool(to_table)), _st())
+
+
+def dsr_splines_order(xi, lut, n_splines, ids=None, order=None, meta=None):
+    """xi [B, H, W] (the clamped interpolated image), lut: the int32 CUDA level table -> (expert id per pixel uint8 [B, H, W],
+    order int32 [B*H*W]: pixel positions by expert, stable; meta int32: 257 segment offsets, 257 first tiles, tile -> expert).
+    No host read; the grids depend on the pixel count and n_splines alone."""
+    _chk(xi, lut)
+    assert xi.dtype == torch.float32 and xi.is_contiguous() and lut.dtype == torch.int32 and lut.numel() == 256
+    N = xi.numel()
+    nm, nh = ctypes.c_long(0), ctypes.c_long(0)
+    call("srhip_dsr_splines_order_sizes", N, n_splines, ctypes.addressof(nm), ctypes.addressof(nh))
+    dev = xi.device
+    if ids is None:
+        ids = torch.empty(xi.shape, dtype=torch.uint8, device=dev)
+    if order is None:
+        order = torch.empty(N, dtype=torch.int32, device=dev)
+    if meta is None:
+        meta = torch.empty(nm.value, dtype=torch.int32, device=dev)
+    assert ids.numel() == N and ids.dtype == torch.uint8 and order.numel() == N and meta.numel() >= nm.value
+    hist = SCRATCH.get("dsr_hist", nh.value, torch.int32, dev)
+    call("srhip_dsr_splines_order", _p(xi), N, _p(lut), n_splines, ids.data_ptr(), _p(order), _p(meta), _p(hist), _st())
+    return ids, order, meta
+
+
+def dsr_splines_meta_ints(pixels, n_splines):
+    nm, nh = ctypes.c_long(0), ctypes.c_long(0)
+    call("srhip_dsr_splines_order_sizes", pixels, n_splines, ctypes.addressof(nm), ctypes.addressof(nh))
+    return nm.value
+
+
+def dsr_splines_fwd(xi, table, order, meta, y, n_splines, in_ksz, n_hidden, local, glob):
+    """y [B, H, W] = the owning expert's net at every pixel (+ xi under the global residual); table [n_splines, stride]."""
+    _chk(xi, table, order, meta, y)
+    B, H, W = xi.shape
+    assert xi.is_contiguous() and y.is_contiguous() and y.shape == xi.shape and table.stride(1) == 1
+    call("srhip_dsr_splines_fwd", _p(xi), _p(table), table.stride(0), _p(order), _p(meta), _p(y), B, H, W, n_splines, in_ksz,
+         n_hidden, int(bool(local)), int(bool(glob)), _st())
+    return y
+
+
+def dsr_splines_bwd(xi, dy, table, order, meta, gtable, n_splines, in_ksz, n_hidden, local, glob):
+    """gtable [n_splines, stride] = the parameter gradients (every element written; fixed summation order)."""
+    _chk(xi, dy, table, order, meta, gtable)
+    B, H, W = xi.shape
+    assert xi.is_contiguous() and dy.is_contiguous() and dy.numel() == xi.numel() and table.stride(1) == 1 and gtable.stride(1) == 1
+    n = lib.srhip_dsr_splines_bwd_ws(n_splines, in_ksz, n_hidden, int(bool(local)))
+    ws = SCRATCH.get("dsr_part", n, device=xi.device)
+    call("srhip_dsr_splines_bwd", _p(xi), _p(dy), _p(table), table.stride(0), _p(order), _p(meta), _p(gtable), gtable.stride(0),
+         _p(ws), n, B, H, W, n_splines, in_ksz, n_hidden, int(bool(local)), int(bool(glob)), _st())
+    return gtable
