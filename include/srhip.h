@@ -1053,6 +1053,36 @@ int srhip_dsr_splines_bwd(const float* x_interp, const float* dy, const float* t
                           int B, int H, int W, int n_splines, int in_ksz, int n_hidden, int local_residual,
                           int global_residual, void* stream);
 
+/* ---- test modes (tta.hip): test_pad / test_split / test_x8 / test_split_x8 of dlib/utils/utils_model.py:110-214 as one
+ * gather launch per tile shape, batched forwards, and one merge launch.  Images are float32 planes [N][H][W], N = batch *
+ * channels.  Both tables are read by the kernel from DEVICE memory; the caller passes its host copy as well, which is what the
+ * argument checks read (a kernel never reads outside the image even if the two differ: a job that fails the checks on the
+ * device writes nothing).
+ *   srhip_view_gather: for every job q and plane n,
+ *     out[q][n][th][tw] = ReplicationPad2d((0, tw - vw, 0, th - vh))(augment_img_tensor4(src[n][y0 : y0 + h][x0 : x0 + w], mode))
+ *   -- the slices of test_split_fn (:146-150), the views of test_x8 / test_split_x8 (:187,206; augment_img_tensor4,
+ *   dlib/utils/utils_image.py:490-508: 1 = rot90 + flip rows, 2 = flip rows, 3 = rot90 x3, 4 = rot90 x2 + flip rows, 5 = rot90,
+ *   6 = rot90 x2, 7 = rot90 x3 + flip rows) and the padding of test_pad (:112-114) / the base case of test_split_fn (:142).
+ *   The view is vh x vw = w x h for modes 1, 3, 5, 7 and h x w otherwise; every job of a call fits (th, tw).  A copy: bit-exact.
+ *   srhip_view_merge: dst[n][sf H][sf W] = (1 / K) * sum_{k = 0 .. K-1} inverse_view_k(E_k), the terms added in that order in
+ *   f32 (test_x8 :188-194, test_split_x8 :207-213; inverse of view i = view i except 3 <-> 5, the `8 - i` of :190,209).  E_k,
+ *   the assembled output of view k, is never materialised: it is the quadtree of test_split_fn (:157-163) over view k's
+ *   frame -- level l is h[l] x w[l] low-resolution pixels (h[0] x w[0] = the image under view k), its four quadrants are the
+ *   h[l+1] x w[l+1] corners of it, and the top / left ones own rows / columns [0, side // 2) of the level, the bottom / right
+ *   ones the rest.  The 4^depth leaves of a view lie in `tiles` as [leaf][N][th * sf][tw * sf], leaf = the base-4 number of the
+ *   path from the root (digit 2 * bottom + right), th x tw >= h[depth] x w[depth] (what was padded is not read).  K = 1,
+ *   depth 0 is the crop of test_pad (:116).  One thread per destination pixel, no atomics: the same bits on every run. */
+typedef struct { int y0, x0, h, w, mode; } srhip_view_job;
+int srhip_view_gather(const float* src, int N, int H, int W, const srhip_view_job* jobs_dev, const srhip_view_job* jobs_host,
+                      int njobs, float* out, int th, int tw, void* stream);
+typedef struct {
+  const float* tiles;         /* device pointer */
+  int mode, depth, th, tw;
+  int h[9], w[9];
+} srhip_view_desc;
+int srhip_view_merge(const srhip_view_desc* views_dev, const srhip_view_desc* views_host, int K, float* dst, int N, int H,
+                     int W, int sf, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

@@ -3,7 +3,7 @@
 fused libsrhip training step.
 
 Kept: init_train, feed_data(dict, need_H), optimize_parameters(epoch, step),
-update_learning_rate, test, set_eval_mode / set_train_mode, current_visuals,
+update_learning_rate, test, testx8 (+ test_tta: any test mode), set_eval_mode / set_train_mode, current_visuals,
 current_log, save / save_best / load_network (raw ``netG.state_dict()`` with
 ``torch.save`` -- file-compatible with the reference's ``<iter>_G.pth`` /
 ``G-model.pth``), save_optimizer / load_optimizer / load_optimizers
@@ -290,6 +290,23 @@ class ModelPlain:
             x = self._net_input()
             self.E = self._graph_forward(x) if self._eval_graph_on() else self.netG(x)
         self.netG.train()
+
+    def test_tta(self, mode, refield=32, min_size=256, modulo=1):
+        """``test()`` through one of the reference's test modes (dlib/utils/utils_model.py:51-88: 1 pad, 2 split, 3 x8
+        self-ensemble, 4 split and x8; 0 is the plain forward): tiles and views gathered by one launch per shape, run
+        through netG in batches, merged by one launch (dlib/utils/utils_model.py of this package).  The scale factor is
+        args.scale, 1 where the net's input already has the target size (SRCNN)."""
+        from dlib.utils import utils_model
+        self.netG.eval()
+        sf = 1 if getattr(self.args, 'method', None) == 'SRCNN' else int(self.args.scale)
+        with torch.no_grad():
+            self.E = utils_model.test_mode(self.netG, self._net_input(), mode=int(mode), refield=refield, min_size=min_size,
+                                           sf=sf, modulo=modulo)
+        self.netG.train()
+
+    def testx8(self):
+        """model_plain.py:404-410: the x8 self-ensemble of netG on the current batch."""
+        self.test_tta(3, modulo=1)
 
     # ---- the evaluation forward replayed from a hipGraph (opt-in: args.eval_graph / SRHIP_EVAL_GRAPH=1).  The small
     # networks of the evaluation sweep are a few thousand short launches per forward: their rate is set by the host's

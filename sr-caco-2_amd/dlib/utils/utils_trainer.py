@@ -94,13 +94,24 @@ def reformat_id(img_id: str) -> str:
     return img_id.replace('/', '_')
 
 
+def _model_test(model, args):
+    """model.test(), or -- eval.py --test_mode 1..4 -- the same batch through one of the test modes of
+    dlib/utils/utils_model.py (pad / split / x8 / split and x8) with --test_refield and --test_min_size."""
+    mode = int(getattr(args, 'test_mode', 0) or 0)
+    if mode == 0:
+        model.test()
+    else:
+        model.test_tta(mode, refield=int(getattr(args, 'test_refield', None) or 32),
+                       min_size=int(getattr(args, 'test_min_size', None) or 256))
+
+
 def _forward_with_padding(test_data: dict, model, args):
     """SwinIR evaluation wrapper (utils_trainer.py:829-862): the low-resolution batch is extended
     by FLIPPED STRIPS of itself to the next multiple of the window -- a whole extra window when it
     already is one: 64 -> 72 -- then output and input are cropped back.  Other nets: plain test()."""
     if args.netG['net_type'] != constants.SWINIR:
         model.feed_data(test_data)
-        model.test()
+        _model_test(model, args)
         return model
     model.feed_data(dict(test_data))
     _, _, h_old, w_old = test_data['l_im'].shape
@@ -111,7 +122,7 @@ def _forward_with_padding(test_data: dict, model, args):
     im = torch.cat([im, torch.flip(im[:, :, h_old - h_pad:, :], [2])], 2)      # the pad only is flipped
     im = torch.cat([im, torch.flip(im[:, :, :, w_old - w_pad:], [3])], 3)
     model.L = im
-    model.test()
+    _model_test(model, args)
     model.E = model.E[..., :h_old * args.scale, :w_old * args.scale]
     model.L = model.L[..., :h_old, :w_old]
     return model

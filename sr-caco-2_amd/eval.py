@@ -3,6 +3,7 @@
 (eval.py:46-146) on the libsrhip path:
 
     python eval.py --cudaid 0 --exp_path <folder> [--data_root <datasets>] [--splits_root <folds>]
+                   [--test_mode {0..4} [--test_refield 32] [--test_min_size 256]]
 
 <folder> is a reference-format experiment directory: ``config_model.yml`` (the yaml dump of the
 run's args, utils_parser.py:1397-1401) and ``best-models/G-model.pth`` (raw ``state_dict``,
@@ -44,6 +45,11 @@ def evaluate_pretrained(argv=None):
     ap.add_argument("--exp_path", type=str, default=None)
     ap.add_argument("--data_root", type=str, default=os.environ.get("SRHIP_DATA_ROOT"))
     ap.add_argument("--splits_root", type=str, default=None)
+    ap.add_argument("--test_mode", type=int, default=0, choices=range(5),
+                    help="dlib/utils/utils_model.py test mode of every forward: 0 plain (default), 1 pad, 2 split, "
+                         "3 x8 self-ensemble, 4 split and x8")
+    ap.add_argument("--test_refield", type=int, default=32, help="--test_mode 2 / 4: receptive field of the net")
+    ap.add_argument("--test_min_size", type=int, default=256, help="--test_mode 2 / 4: up to min_size^2 pixels go in whole")
     ns = ap.parse_args(argv)
     exp_path = ns.exp_path
     assert exp_path and isdir(exp_path), exp_path
@@ -70,6 +76,9 @@ def evaluate_pretrained(argv=None):
     torch.cuda.set_device(int(str(ns.cudaid or '0').split(',')[0]))
 
     args.is_train = False
+    if ns.test_mode:
+        args.test_mode, args.test_refield, args.test_min_size = ns.test_mode, ns.test_refield, ns.test_min_size
+        DLLogger.log(f'test mode {ns.test_mode} (refield {ns.test_refield}, min_size {ns.test_min_size})')
     args.netG['checkpoint_path_netG'] = join(exp_path, 'best-models/G-model.pth')
     if args.amp:
         DLLogger.log('config has amp=True: evaluating with the reduced-precision (single bf16 product) kernels')

@@ -2281,3 +2281,70 @@ def dsr_splines_bwd(xi, dy, table, order, meta, gtable, n_splines, in_ksz, n_hid
     call("srhip_dsr_splines_bwd", _p(xi), _p(dy), _p(table), table.stride(0), _p(order), _p(meta), _p(gtable), gtable.stride(0),
          _p(ws), n, B, H, W, n_splines, in_ksz, n_hidden, int(bool(local)), int(bool(glob)), _st())
     return gtable
+
+
+# ------------------------------------------------------------------ test modes (tta.hip)
+class _ViewJob(ctypes.Structure):    # srhip_view_job (include/srhip.h)
+    _fields_ = [("y0", ctypes.c_int), ("x0", ctypes.c_int), ("h", ctypes.c_int), ("w", ctypes.c_int), ("mode", ctypes.c_int)]
+
+
+class _ViewDesc(ctypes.Structure):   # srhip_view_desc (include/srhip.h)
+    _fields_ = [("tiles", ctypes.c_void_p), ("mode", ctypes.c_int), ("depth", ctypes.c_int), ("th", ctypes.c_int),
+                ("tw", ctypes.c_int), ("h", ctypes.c_int * 9), ("w", ctypes.c_int * 9)]
+
+
+def _to_device_table(arr, device):
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+
+
+def _planes(x, what):
+    if not (torch.is_tensor(x) and x.is_cuda):
+        raise SrhipError(f"{what}: GPU only (no CPU fallback exists)")
+    if x.dtype != torch.float32 or x.dim() < 2:
+        raise SrhipError(f"{what}: float32 planes [..., H, W] (got {x.dtype}, {tuple(x.shape)})")
+    if not x.is_contiguous():
+        raise SrhipError(f"{what}: the planes must be contiguous")
+    return x.numel() // (x.shape[-2] * x.shape[-1]), x.shape[-2], x.shape[-1]
+
+
+def view_gather(src, jobs, th, tw, out=None):
+    """[len(jobs), *src.shape[:-2], th, tw]: for every job (y0, x0, h, w, mode) the rectangle of every plane of ``src``
+    [..., H, W] under dihedral view ``mode`` (utils_image.augment_img_tensor4), replicate-padded right / bottom to (th, tw).
+    One launch (srhip_view_gather); the job table is uploaded here."""
+    N, H, W = _planes(src, "view_gather")
+    host = (_ViewJob * len(jobs))(*[_ViewJob(*map(int, j)) for j in jobs])
+    if out is None:
+        out = torch.empty((len(jobs),) + tuple(src.shape[:-2]) + (int(th), int(tw)), dtype=torch.float32, device=src.device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == len(jobs) * N * th * tw):
+        raise SrhipError("view_gather: out must be a contiguous float32 CUDA tensor of jobs * planes * th * tw elements")
+    dev = _to_device_table(host, src.device)
+    call("srhip_view_gather", _p(src), N, H, W, _p(dev), ctypes.addressof(host), len(jobs), _p(out), int(th), int(tw), _st())
+    return out
+
+
+def view_merge(views, N, H, W, sf, out=None):
+    """[N, sf H, sf W] = the mean over ``views`` of the inverse view of each view's assembled tiles (srhip_view_merge, one
+    launch, fixed summation order).  A view is (tiles, mode, th, tw, levels): ``tiles`` a contiguous float32 CUDA tensor
+    [4^depth, N, th * sf, tw * sf] in leaf order, ``levels`` the depth + 1 (h, w) of the split's levels in the view's frame."""
+    K = len(views)
+    if K == 0:
+        raise SrhipError("view_merge: no view")
+    host = (_ViewDesc * K)()
+    for d, (tiles, mode, th, tw, levels) in zip(host, views):
+        depth = len(levels) - 1
+        if not 0 <= depth <= 8:
+            raise SrhipError(f"view_merge: split depth 0..8 (got {depth})")
+        n_t, _, _ = _planes(tiles, "view_merge")
+        if n_t != (4 ** depth) * N or tuple(tiles.shape[-2:]) != (th * sf, tw * sf):
+            raise SrhipError(f"view_merge: tiles {tuple(tiles.shape)} are not 4^{depth} x {N} planes of {th * sf} x {tw * sf}")
+        d.tiles, d.mode, d.depth, d.th, d.tw = tiles.data_ptr(), int(mode), depth, int(th), int(tw)
+        for l, (h, w) in enumerate(levels):
+            d.h[l], d.w[l] = int(h), int(w)
+    device = views[0][0].device
+    if out is None:
+        out = torch.empty(N, H * sf, W * sf, dtype=torch.float32, device=device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == N * H * sf * W * sf):
+        raise SrhipError("view_merge: out must be a contiguous float32 CUDA tensor of N * sf H * sf W elements")
+    dev = _to_device_table(host, device)
+    call("srhip_view_merge", _p(dev), ctypes.addressof(host), K, _p(out), int(N), int(H), int(W), int(sf), _st())
+    return out
