@@ -392,7 +392,13 @@ __device__ __forceinline__ float sigmoid_f(float z) { return 1.f / (1.f + expf(-
 // |x - cs_k| > sqrt(104 c2), which bounds the bins a pixel touches the same way.
 template <int MODE>
 __device__ __forceinline__ float bin_center(int k, float delta, int bins) {
-  if (MODE == 0) return delta * ((float)k + 0.5f);
+  // the reference's centres are a float32 tensor: the product ROUNDED.  Left to the compiler, x - delta * (k + 0.5) becomes one
+  // fused multiply-add on the unrounded product, which moves every bin edge by up to half an ulp of the centre (3e-8):
+  // times sigma, 1.5e-4 in the sigmoid's argument at sigma = 5e3 (the pragma keeps the product out of the caller's subtraction)
+  if (MODE == 0) {
+#pragma clang fp contract(off)
+    return delta * ((float)k + 0.5f);
+  }
   // torch.linspace(0, 1, bins): from the start below the middle, from the end above it
   return k < bins / 2 ? delta * (float)k : 1.f - delta * (float)(bins - 1 - k);
 }
@@ -584,7 +590,8 @@ int srhip_loss_local_moments(const float* pred, const float* target, float* grad
   return 0;
 }
 
-long srhip_loss_hist_ws(int B, int bins) { return (long)B * HB * 2 * bins + (long)B * bins + 2L * B; }
+// partial histograms, dL/dh, one float of padding where B * bins is odd (the doubles behind it are 8-byte aligned), B doubles
+long srhip_loss_hist_ws(int B, int bins) { return (long)B * HB * 2 * bins + (long)B * bins + (((long)B * bins) & 1) + 2L * B; }
 
 int srhip_loss_hist(const float* pred, const float* target, float* grad, float* loss_out, float* workspace, int B,
                     long n, int bins, float sigma, int norm, float lam, int grad_accum, int loss_accum, float elb_t,

@@ -827,7 +827,7 @@ __global__ void k_nonfinite(const float* __restrict__ x, long n, int* __restrict
 __global__ void k_axpby(float* __restrict__ y, const float* __restrict__ x, long n, float a, float b) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n;
        i += (long)gridDim.x * blockDim.x)
-    y[i] = a * x[i] + b * y[i];
+    y[i] = b != 0.f ? a * x[i] + b * y[i] : a * x[i];   // b == 0: y is an output only (0 * NaN would keep a stale NaN), as k_axpby2d
 }
 
 inline int ew_grid(long n) {
