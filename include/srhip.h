@@ -1083,6 +1083,25 @@ typedef struct {
 int srhip_view_merge(const srhip_view_desc* views_dev, const srhip_view_desc* views_host, int K, float* dst, int N, int H,
                      int W, int sf, void* stream);
 
+/* ---- prediction on images without an HR partner (io.hip; srhip/predict.py): the device passes around the forward, one launch
+ * each.  Pages are 8-bit, or 16-bit in the machine's (little-endian) byte order, as PIL hands them out.
+ *   srhip_ingest_pad: B pages [H][W] of `bits` (8 / 16) -> float32 [B][Hp][Wp],
+ *     value: np.float32(min(v, in_max) / float(in_max)) -- the quotient in double, then rounded to float32: uint2single /
+ *     uint162single (dlib/utils/utils_image.py:322-331) for in_max = 255 / 65535; another in_max (4095: 12-bit data in a 16-bit
+ *     container) saturates the values above it to 1.0.  1 <= in_max <= 2^bits - 1.
+ *     padding: _forward_with_padding (dlib/utils/utils_trainer.py:829-862), `cat([im, flip(im[:, :, H - h_pad:, :], [2])], 2)`
+ *     then the same along the columns of the row-padded image: row H + k is row H - 1 - k, then column W + k is column
+ *     W - 1 - k (the corner is flipped both ways).  Hp == H and Wp == W: no padding.  Hp - H > H or Wp - W > W is an error: the
+ *     reference's slice would start at a negative index.
+ *   srhip_emit_uint: float32 [B][Hs][Ws] -> B pages [Ho][Wo] of `bits` (8 / 16), the top-left rectangle (Ho <= Hs, Wo <= Ws:
+ *     the crop `E[..., :h_old * scale, :w_old * scale]` of :860),
+ *     value: round_half_even(clamp(x, 0, 1) * (2^bits - 1)), ONE float32 product: tensor2uint / single2uint16
+ *     (utils_image.py:334-335,362-366).  NaN stores 0, +-inf what the clamp gives.
+ *     nonfinite (device int, may be NULL) is set to 1 when a pixel INSIDE the crop is NaN or +-inf; it is never cleared here.
+ * Both are copies with exactly rounded arithmetic: bit-exact against the numpy / torch statements. */
+int srhip_ingest_pad(const void* src, int bits, int in_max, int B, int H, int W, float* dst, int Hp, int Wp, void* stream);
+int srhip_emit_uint(const float* x, int B, int Hs, int Ws, void* dst, int bits, int Ho, int Wo, int* nonfinite, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

@@ -2348,3 +2348,43 @@ def view_merge(views, N, H, W, sf, out=None):
     dev = _to_device_table(host, device)
     call("srhip_view_merge", _p(dev), ctypes.addressof(host), K, _p(out), int(N), int(H), int(W), int(sf), _st())
     return out
+
+
+# ------------------------------------------------------------------ prediction I/O (io.hip)
+_UINT_BITS = {torch.uint8: 8, torch.uint16: 16}
+
+
+def ingest_pad(src, in_max, Hp, Wp, out=None):
+    """uint8 / uint16 pages [B, H, W] -> float32 [B, Hp, Wp] = np.float32(min(v, in_max) / float(in_max)) (util.uint2single /
+    uint162single), extended by flipped strips as _forward_with_padding does (rows first, then the columns of the row-padded
+    image); Hp == H, Wp == W: no padding.  One launch (srhip_ingest_pad)."""
+    if not (torch.is_tensor(src) and src.is_cuda):
+        raise SrhipError("ingest_pad: GPU only (no CPU fallback exists)")
+    if src.dtype not in _UINT_BITS or src.dim() != 3 or not src.is_contiguous():
+        raise SrhipError(f"ingest_pad: contiguous uint8 / uint16 pages [B, H, W] (got {src.dtype}, {tuple(src.shape)})")
+    B, H, W = src.shape
+    if out is None:
+        out = torch.empty(B, int(Hp), int(Wp), dtype=torch.float32, device=src.device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * Hp * Wp):
+        raise SrhipError("ingest_pad: out must be a contiguous float32 CUDA tensor of B * Hp * Wp elements")
+    call("srhip_ingest_pad", _p(src), _UINT_BITS[src.dtype], int(in_max), B, H, W, _p(out), int(Hp), int(Wp), _st())
+    return out
+
+
+def emit_uint(x, bits, Ho, Wo, flag=None, out=None):
+    """float32 planes [..., Hs, Ws] -> uint8 (bits 8) / uint16 (bits 16) pages [..., Ho, Wo] of the top-left rectangle,
+    round_half_even(clamp(x, 0, 1) * (2^bits - 1)) with one float32 product (util.tensor2uint / single2uint16).  ``flag``: an
+    int32 CUDA tensor of one element, set to 1 when a pixel inside the rectangle is NaN or +-inf (NaN stores 0); it is not
+    cleared here.  One launch (srhip_emit_uint)."""
+    N, Hs, Ws = _planes(x, "emit_uint")
+    dtype = {8: torch.uint8, 16: torch.uint16}.get(bits)
+    if dtype is None:
+        raise SrhipError(f"emit_uint: bits 8 or 16 (got {bits})")
+    if flag is not None and not (torch.is_tensor(flag) and flag.is_cuda and flag.dtype == torch.int32 and flag.numel() == 1):
+        raise SrhipError("emit_uint: flag must be an int32 CUDA tensor of one element")
+    if out is None:
+        out = torch.empty(tuple(x.shape[:-2]) + (int(Ho), int(Wo)), dtype=dtype, device=x.device)
+    elif not (out.is_cuda and out.dtype == dtype and out.is_contiguous() and out.numel() == N * Ho * Wo):
+        raise SrhipError(f"emit_uint: out must be a contiguous {dtype} CUDA tensor of planes * Ho * Wo elements")
+    call("srhip_emit_uint", _p(x), N, Hs, Ws, _p(out), int(bits), int(Ho), int(Wo), _p(flag), _st())
+    return out
