@@ -13,14 +13,18 @@ LIB_PATH = os.environ.get("SRHIP_LIB") or os.path.join(os.path.dirname(_HERE), "
 HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "srhip.h")
 _CT = {"p": ctypes.c_void_p, "l": ctypes.c_long, "i": ctypes.c_int, "u": ctypes.c_uint,
        "f": ctypes.c_float, "d": ctypes.c_double}
+_BASE = {"long": "l", "int": "i", "unsigned": "u", "float": "f", "double": "d"}
+
+
+def _header_text(path=HEADER):
+    return re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
 
 
 def parse_header(path=HEADER):
     """include/srhip.h is the single source of truth: returns
     {name: (return_code, arg_codes)} with p pointer, l long, i int, u unsigned int,
     f float, d double, s const char*."""
-    text = open(path).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = _header_text(path)
     protos = {}
     for m in re.finditer(r"(const char\*|int|long)\s+(srhip_\w+)\s*\(([^)]*)\)\s*;", text):
         ret, name, args = m.group(1), m.group(2), m.group(3).strip()
@@ -31,9 +35,56 @@ def parse_header(path=HEADER):
                 if "*" in a:
                     codes += "p"
                 else:
-                    codes += {"long": "l", "int": "i", "unsigned": "u", "float": "f", "double": "d"}[a.split()[0]]
+                    codes += _BASE[a.split()[0]]
         protos[name] = ({"const char*": "s", "int": "i", "long": "l"}[ret], codes)
     return protos
+
+
+_DECLARATOR = re.compile(r"([\w\s]*?)([\s*]*)\b(\w+)\s*(?:\[\s*(\d+)\s*\])?")
+
+
+def parse_structs(text=None):
+    """{C name: ctypes.Structure subclass} of every ``typedef struct [tag] { ... } name;`` of the header (or of ``text``):
+    any ``*`` is a c_void_p, int / long / unsigned / float / double as in _CT, ``name[N]`` an array, the declarators of a comma
+    list share the base type but not the ``*``.  Anything else (another base type, a nested struct, a bit-field, a function
+    pointer) raises with the struct and the declaration: a layout is never guessed."""
+    text = _header_text() if text is None else re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    structs = {}
+    for m in re.finditer(r"typedef\s+struct\s*\w*\s*\{", text):
+        end, depth = m.end(), 1
+        while depth:        # the brace that closes the struct, past any nested ones
+            depth += {"{": 1, "}": -1}.get(text[end], 0)
+            end += 1
+        name = re.match(r"\s*(\w+)\s*;", text[end:]).group(1)
+        body = text[m.end():end - 1]
+
+        def refuse(decl):
+            return ValueError(f"struct {name}: cannot take the layout of {' '.join(decl.split())!r}")
+        if "{" in body:
+            raise refuse(body)
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            base = None
+            for item in decl.split(","):
+                d = _DECLARATOR.fullmatch(item.strip())
+                words = d and [w for w in d.group(1).split() if w != "const"]
+                if not d or (base is None) != bool(words):
+                    raise refuse(decl)
+                base = " ".join(words) if base is None else base
+                if "*" not in d.group(2) and base not in _BASE:
+                    raise refuse(decl)
+                ct = ctypes.c_void_p if "*" in d.group(2) else _CT[_BASE[base]]
+                fields.append((d.group(3), ct * int(d.group(4)) if d.group(4) else ct))
+        structs[name] = type(name, (ctypes.Structure,), {"_fields_": fields})
+    return structs
+
+
+_STRUCTS = parse_structs()
+
+
+def struct(name):
+    """the ctypes mirror of a struct of include/srhip.h, by its C name"""
+    return _STRUCTS[name]
 
 
 def _load():

@@ -15,10 +15,9 @@ residual + ReLU, srhip_conv3x3_nhwc_split_ex epi 8), the 128->1 edge conv.  The 
 shared convs are summed over the U applications.
 """
 import torch
-import torch.nn.functional as F
 
 from . import ops
-from .swinir_engine import _Bufs
+from .swinir_engine import _Bufs, bicubic_clamped
 
 CH = 128
 
@@ -48,29 +47,10 @@ class DRRNEngine:
         return [("wa", ru[1]), ("wb", ru[3])]
 
     def prepare(self):
-        D, ws = self.derived, self.ws
-        dev = self.net.conv2[1].weight.device
-        if ws.use_bx3:
-            sig = tuple(p.data_ptr() for p in self.net.parameters())
-            if self._prep is None or sig != self._prep_sig:
-                tb = ops.PrepTable()
-                for name, conv in self._convs():
-                    tb.conv(conv.weight.data, ws.planes(name + ".wp", 9 * CH, CH, dev))
-                    tb.conv(conv.weight.data, ws.planes(name + ".wpt", 9 * CH, CH, dev), data_grad=True)
-                self._prep, self._prep_sig = tb.build(dev), sig
-            self._prep.run()
-        else:
-            for name, conv in self._convs():
-                ops.pack_conv_weight(conv.weight.data, D.get(name + ".wp", 9, CH, CH, device=dev),
-                                     D.get(name + ".wpt", 9, CH, CH, device=dev))
-                ws.register(name + ".wp", D.d[name + ".wp"])
-                ws.register(name + ".wpt", D.d[name + ".wpt"])
-        self.prepared = True
+        ops.prepare_conv_packs(self, ((name, conv.weight.data, False) for name, conv in self._convs()))
 
     def interpolate(self, x):
-        s = self.net.upscale
-        out = F.interpolate(x, size=(s * x.shape[2], s * x.shape[3]), mode='bicubic', align_corners=False)
-        return torch.clamp(out, min=0.0, max=1.0)[:, 0].contiguous()
+        return bicubic_clamped(x, self.net.upscale)
 
     def amp_train_ok(self):
         """Whether this configuration trains under --amp on fp16 storage (forward_h16(save=True) + backward_h16): the fp16x2

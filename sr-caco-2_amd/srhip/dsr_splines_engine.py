@@ -13,10 +13,9 @@ parameter and gradient buffers already ARE the kernels' [n_splines, P] tables (t
 used in place when the views line up (data_ptr check); otherwise one launch packs the tensors into a table of the
 engine's own (module path) and one unpacks the gradients."""
 import torch
-import torch.nn.functional as F
 
 from . import ops
-from .swinir_engine import _Bufs
+from .swinir_engine import _Bufs, bicubic_clamped
 
 
 class DsrSplinesEngine:
@@ -95,9 +94,7 @@ class DsrSplinesEngine:
     # ---- forward / backward
     def interpolate(self, x):
         """network_dsr_splines.py:376-387: [B,1,h,w] -> [B,s*h,s*w], bicubic (align_corners False), clamped."""
-        s = self.net.upscale
-        out = F.interpolate(x, size=(s * x.shape[2], s * x.shape[3]), mode='bicubic', align_corners=False)
-        return torch.clamp(out, min=0.0, max=1.0)[:, 0].contiguous()
+        return bicubic_clamped(x, self.net.upscale)
 
     def forward(self, x, dp=None, save=True):
         """x [B,h,w] (LR) -> [B,1,s*h,s*w]."""

@@ -70,27 +70,9 @@ class EDSREngine:
             yield f"up{i}", net.tail[0][2 * i]
 
     def prepare(self):
-        D, ws = self.derived, self.ws
-        dev = self.net.head[0].weight.device
-        if ws.use_bx3:      # all conv packs as bf16x3 planes by one launch
-            sig = tuple(p.data_ptr() for p in self.net.parameters())
-            if self._prep is None or sig != self._prep_sig:
-                tb = ops.PrepTable()
-                for name, conv in self._body_convs():
-                    co, ci = conv.weight.shape[:2]
-                    ps2 = self.fuse_ps and name.startswith("up")
-                    tb.conv(conv.weight.data, ws.planes(name + ".wp", 9 * co, ci, dev), ps2=ps2)
-                    tb.conv(conv.weight.data, ws.planes(name + ".wpt", 9 * ci, co, dev), data_grad=True, ps2=ps2)
-                self._prep, self._prep_sig = tb.build(dev), sig
-            self._prep.run()
-        else:
-            for name, conv in self._body_convs():
-                co, ci = conv.weight.shape[:2]
-                ops.pack_conv_weight(conv.weight.data, D.get(name + ".wp", 9, co, ci, device=dev),
-                                     D.get(name + ".wpt", 9, ci, co, device=dev))
-                ws.register(name + ".wp", D.d[name + ".wp"])
-                ws.register(name + ".wpt", D.d[name + ".wpt"])
-        self.prepared = True
+        # planes: all conv packs by one launch, the upsampler's in the order of its fused PixelShuffle
+        ops.prepare_conv_packs(self, ((name, conv.weight.data, self.fuse_ps and name.startswith("up"))
+                                      for name, conv in self._body_convs()))
 
     # ------------------------------------------------------------------ forward
     def _h16_ok(self):

@@ -21,10 +21,9 @@ On the device (NHWC, T = B*H*W pixels):
                  applied ``num_residual_blocks`` times) in one batched launch, summed per shared weight.
 """
 import torch
-import torch.nn.functional as F
 
 from . import ops
-from .swinir_engine import _Bufs
+from .swinir_engine import _Bufs, bicubic_clamped
 
 CH = 64
 GEMM_BYTES_MAX = (1 << 31) - 1
@@ -76,9 +75,7 @@ class MemNetEngine:
                 for j in range(self.R):
                     seq = mb.recursive_unit[j].residual_block
                     for c, idx in ((0, 2), (1, 5)):
-                        w = seq[idx].weight.data
-                        tb.conv(w, ws.planes(f"m{i}.u{j}.c{c}.wp", 9 * CH, CH, dev))
-                        tb.conv(w, ws.planes(f"m{i}.u{j}.c{c}.wpt", 9 * CH, CH, dev), data_grad=True)
+                        tb.conv_pair(f"m{i}.u{j}.c{c}", seq[idx].weight.data, ws)
                 gw = mb.gate_unit[2].weight.data.view(CH, self._gc(i))
                 tb.linear(gw, ws.planes(f"m{i}.gw", CH, self._gc(i), dev))
                 tb.linear(gw, ws.planes(f"m{i}.gwt", self._gc(i), CH, dev), transpose=True)
@@ -118,9 +115,7 @@ class MemNetEngine:
 
     def interpolate(self, x):
         """network_memnet.py:127-139: [B,1,h,w] -> [B,s*h,s*w], bicubic (align_corners False), clamped."""
-        s = self.net.upscale
-        out = F.interpolate(x, size=(s * x.shape[2], s * x.shape[3]), mode='bicubic', align_corners=False)
-        return torch.clamp(out, min=0.0, max=1.0)[:, 0].contiguous()
+        return bicubic_clamped(x, self.net.upscale)
 
     def _prepare_h16(self, dev):
         """the gate units' 1x1 convs as the centre tap of 3x3 weights, in the fp16x2 conv operand format (conv_h16.hip)"""

@@ -96,11 +96,8 @@ class MSLapSRNEngine:
             D.get(f"o{o}.w4f", 1, 4, 3, 3, device=dev).copy_(w4.flip(2, 3).reshape(1, 4, 3, 3))
             if rebuild:
                 for k in range(10):
-                    w = a[k].cl[0].weight.data
-                    tb.conv(w, ws.planes(f"o{o}.c{k}.wp", 9 * CH, CH, dev))
-                    tb.conv(w, ws.planes(f"o{o}.c{k}.wpt", 9 * CH, CH, dev), data_grad=True)
-                tb.conv(wc, ws.planes(f"o{o}.up.wp", 9 * 4 * CH, CH, dev), ps2=True)
-                tb.conv(wc, ws.planes(f"o{o}.up.wpt", 9 * CH, 4 * CH, dev), data_grad=True, ps2=True)
+                    tb.conv_pair(f"o{o}.c{k}", a[k].cl[0].weight.data, ws)
+                tb.conv_pair(f"o{o}.up", wc, ws, ps2=True)
         if rebuild:
             self._prep, self._prep_sig = tb.build(dev), sig
         self._prep.run()

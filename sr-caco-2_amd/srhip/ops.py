@@ -9,7 +9,7 @@ import ctypes
 import torch
 
 from . import probe
-from ._lib import call, lib, SrhipError  # noqa: F401
+from ._lib import call, lib, struct, SrhipError  # noqa: F401
 
 
 def _chk(*ts):
@@ -140,13 +140,7 @@ def split_bf16x3(W):
     return Bx3(W2d.shape[0], W2d.shape[1], W.device).fill(W2d)
 
 
-class _PrepEntry(ctypes.Structure):   # srhip_prep_entry (include/srhip.h)
-    _fields_ = [("a", ctypes.c_void_p), ("b", ctypes.c_void_p), ("c", ctypes.c_void_p),
-                ("out", ctypes.c_void_p), ("out2", ctypes.c_void_p),
-                ("kind", ctypes.c_int), ("blk0", ctypes.c_int),
-                ("n0", ctypes.c_int), ("n1", ctypes.c_int), ("n2", ctypes.c_int),
-                ("s0", ctypes.c_int), ("s1", ctypes.c_int), ("s2", ctypes.c_int), ("off", ctypes.c_int),
-                ("mode", ctypes.c_int)]
+_PrepEntry = struct("srhip_prep_entry")
 
 
 class PrepTable:
@@ -209,6 +203,13 @@ class PrepTable:
             self._add(kind=kind, a=_p(w), out=_p(out.planes), n0=Co, n1=9, n2=Ci, s0=1, s1=Ci * 9, s2=9, off=0,
                       mode=12 if ps2 else 0)
 
+    def conv_pair(self, name, w, ws, ps2=False):
+        """both directions of the 3x3 conv weight w [Co,Ci,3,3] on planes of the WeightSet ``ws``: the forward pack under
+        ``name + ".wp"``, the data-gradient twin under ``name + ".wpt"`` (two jobs, in this order)"""
+        Co, Ci = w.shape[:2]
+        self.conv(w, ws.planes(name + ".wp", 9 * Co, Ci, w.device), ps2=ps2)
+        self.conv(w, ws.planes(name + ".wpt", 9 * Ci, Co, w.device), data_grad=True, ps2=ps2)
+
     def fold_bias(self, W, b, beta, out):
         N, K = W.shape
         self.keep += [W, b, beta, out]
@@ -257,8 +258,37 @@ class WeightSet:
             bx = self.d[key] = Bx3(rows, K, device)
         return bx
 
+    def pack_conv(self, name, w, bufs):
+        """the exact-f32 counterpart of PrepTable.conv_pair: the tap-major packs [9][Co][Ci] / [9][Ci][Co] of w
+        [Co,Ci,3,3] (srhip_pack_conv_weight) in buffers of ``bufs``, registered under ``name + ".wp"`` / ``".wpt"``"""
+        Co, Ci = w.shape[:2]
+        wp, wpt = bufs.get(name + ".wp", 9, Co, Ci, device=w.device), bufs.get(name + ".wpt", 9, Ci, Co, device=w.device)
+        pack_conv_weight(w, wp, wpt)
+        self.register(name + ".wp", wp)
+        self.register(name + ".wpt", wpt)
+
     def __getitem__(self, key):
         return self.d[key]
+
+
+def prepare_conv_packs(eng, convs):
+    """prepare() of an engine whose derived weights are the packs of its 3x3 convs, ``convs`` an iterable of (name, weight
+    [Co,Ci,3,3], ps2) -- read only when the packs are laid out, so a generator costs a steady-state step nothing.  Planes:
+    one job table, built when first needed and again when a parameter of eng.net moved (data_ptr), otherwise only re-run;
+    exact-f32 kernels: the packs in eng.derived."""
+    ws = eng.ws
+    if ws.use_bx3:
+        sig = tuple(p.data_ptr() for p in eng.net.parameters())
+        if eng._prep is None or sig != eng._prep_sig:
+            tb = PrepTable()
+            for name, w, ps2 in convs:
+                tb.conv_pair(name, w, ws, ps2=ps2)
+            eng._prep, eng._prep_sig = tb.build(w.device), sig
+        eng._prep.run()
+    else:
+        for name, w, _ in convs:
+            ws.pack_conv(name, w, eng.derived)
+    eng.prepared = True
 
 
 def gemm_nt(A, W, bias=None, out=None, a_mode=0, ln_stats=None, epi=0, R=None,
@@ -964,8 +994,24 @@ def conv3x3_ps2_bwd_data_h16(dYup, Wpt, out):
     return out
 
 
-class _ConvWgradH16Item(ctypes.Structure):   # srhip_conv_wgrad_h16_item (include/srhip.h)
-    _fields_ = [("dY", ctypes.c_void_p), ("X", ctypes.c_void_p), ("dW", ctypes.c_void_p), ("db", ctypes.c_void_p)]
+_ConvWgradH16Item = struct("srhip_conv_wgrad_h16_item")
+
+
+def _pf(t):
+    """pointer of an f32 CUDA tensor (or None): _ph's counterpart"""
+    _chk(t)
+    return _p(t)
+
+
+def _wgrad_items(Item, ptr, items, dY0, X0, Cout, Cin):
+    """the item table of one conv weight-gradient launch: every (dY, X, dW, db) of the shapes of dY0 / X0, dense"""
+    arr = (Item * len(items))()
+    for a, (dY, X, dW, db) in zip(arr, items):
+        _chk(dW, db)
+        assert dY.shape == dY0.shape and X.shape == X0.shape and dY.is_contiguous() and X.is_contiguous()
+        assert dW.is_contiguous() and tuple(dW.shape) == (Cout, Cin, 3, 3)
+        a.dY, a.X, a.dW, a.db = ptr(dY), ptr(X), _p(dW), _p(db)
+    return arr
 
 
 def conv3x3_wgrad_h16(items, ps2=False):
@@ -983,12 +1029,7 @@ def conv3x3_wgrad_h16(items, ps2=False):
         per = ctypes.c_long(0)
         call("srhip_conv3x3_wgrad_h16_plan", n, B, H, W, Cout, Cin, int(bool(ps2)), ctypes.addressof(S), ctypes.addressof(per))
         part = SCRATCH.get("wgh16_part", n * per.value, device=dY0.device)
-        arr = (_ConvWgradH16Item * n)()
-        for k, (dY, X, dW, db) in enumerate(chunk):
-            _chk(dW, db)
-            assert dY.shape == dY0.shape and X.shape == X0.shape and dY.is_contiguous() and X.is_contiguous()
-            assert dW.is_contiguous() and tuple(dW.shape) == (Cout, Cin, 3, 3)
-            arr[k].dY, arr[k].X, arr[k].dW, arr[k].db = _ph(dY), _ph(X), _p(dW), _p(db)
+        arr = _wgrad_items(_ConvWgradH16Item, _ph, chunk, dY0, X0, Cout, Cin)
 
         def run():
             call("srhip_conv3x3_wgrad_h16", ctypes.addressof(arr), n, dY0.stride(2), X0.stride(2), B, H, W, Cout, Cin,
@@ -1040,12 +1081,7 @@ def conv3x3_wgrad_shared_h16(items, accumulate):
     per = ctypes.c_long(0)
     call("srhip_conv3x3_wgrad_shared_h16_plan", n, B, H, W, Cout, Cin, ctypes.addressof(S), ctypes.addressof(per))
     part = SCRATCH.get("wgsh16_part", n * per.value, device=dY0.device)
-    arr = (_ConvWgradH16Item * n)()
-    for k, (dY, X, dW, db) in enumerate(items):
-        _chk(dW, db)
-        assert dY.shape == dY0.shape and X.shape == X0.shape and dY.is_contiguous() and X.is_contiguous()
-        assert dW.is_contiguous() and tuple(dW.shape) == (Cout, Cin, 3, 3)
-        arr[k].dY, arr[k].X, arr[k].dW, arr[k].db = _ph(dY), _ph(X), _p(dW), _p(db)
+    arr = _wgrad_items(_ConvWgradH16Item, _ph, items, dY0, X0, Cout, Cin)
 
     def run():
         call("srhip_conv3x3_wgrad_shared_h16", ctypes.addressof(arr), n, dY0.stride(2), X0.stride(2), B, H, W, Cout, Cin,
@@ -1204,19 +1240,10 @@ def linear_wgrad(dY, X, dW, db, a_rowscale=None, a_rowscale_rows=1, b_mode=0, ln
              _p(dW), _p(db), _p(dgamma), _p(dbeta), N, K, _p(lnws), _st())
 
 
-class _TnProblem(ctypes.Structure):   # srhip_tn_problem (include/srhip.h)
-    _fields_ = [("A", ctypes.c_void_p), ("lda", ctypes.c_long), ("B", ctypes.c_void_p),
-                ("ldb", ctypes.c_long), ("NI", ctypes.c_int), ("NJ", ctypes.c_int),
-                ("a_rowscale", ctypes.c_void_p), ("a_rowscale_rows", ctypes.c_int),
-                ("b_mode", ctypes.c_int), ("ln_stats", ctypes.c_void_p),
-                ("part", ctypes.c_void_p), ("part_colsum", ctypes.c_void_p)]
+_TnProblem = struct("srhip_tn_problem")
 
 
-class _ReduceProblem(ctypes.Structure):   # srhip_reduce_problem (include/srhip.h)
-    _fields_ = [("part", ctypes.c_void_p), ("colsum", ctypes.c_void_p), ("W", ctypes.c_void_p),
-                ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p), ("dW", ctypes.c_void_p),
-                ("db", ctypes.c_void_p), ("dgamma", ctypes.c_void_p), ("dbeta", ctypes.c_void_p),
-                ("N", ctypes.c_int), ("K", ctypes.c_int), ("ln_ws", ctypes.c_void_p)]
+_ReduceProblem = struct("srhip_reduce_problem")
 
 
 def linear_wgrad_grouped(problems):
@@ -1387,8 +1414,7 @@ def conv3x3_wgrad(dY, X, dW, db, ps2=False):
     call("srhip_reduce_conv_wgrad", _p(part), _p(cs), S, _p(dW), _p(db), Cout, Cin, _st())
 
 
-class _ConvWgradItem(ctypes.Structure):   # srhip_conv_wgrad_item (include/srhip.h)
-    _fields_ = [("dY", ctypes.c_void_p), ("X", ctypes.c_void_p), ("dW", ctypes.c_void_p), ("db", ctypes.c_void_p)]
+_ConvWgradItem = struct("srhip_conv_wgrad_item")
 
 
 def conv3x3_wgrad_batched(items):
@@ -1407,12 +1433,7 @@ def conv3x3_wgrad_batched(items):
         call("srhip_conv3x3_wgrad_batched_plan", n, B, H, W, Cout, Cin, ctypes.addressof(S), ctypes.addressof(per))
         part = SCRATCH.get("tnb_part", n * per.value, device=dY0.device)
         cs = SCRATCH.get("tnb_colsum", n * S.value * Cout, device=dY0.device)
-        arr = (_ConvWgradItem * n)()
-        for k, (dY, X, dW, db) in enumerate(chunk):
-            _chk(dY, X, dW, db)
-            assert dY.shape == dY0.shape and X.shape == X0.shape and dY.stride(2) == dY0.stride(2) \
-                and X.stride(2) == X0.stride(2) and dY.is_contiguous() and X.is_contiguous()
-            arr[k].dY, arr[k].X, arr[k].dW, arr[k].db = _p(dY), _p(X), _p(dW), _p(db)
+        arr = _wgrad_items(_ConvWgradItem, _pf, chunk, dY0, X0, Cout, Cin)      # same shape, dense: the same strides
 
         def run():
             call("srhip_conv3x3_wgrad_batched_bx3", ctypes.addressof(arr), n, dY0.stride(2), X0.stride(2), B, H, W,
@@ -1792,54 +1813,40 @@ def loss_stencil(pred, target, kind, lam=1.0, norm=2, ksz=3, channel_norm=False,
 
 
 # ------------------------------------------------------------------ input pipeline (f2)
-class _PatchJob(ctypes.Structure):   # srhip_patch_job (include/srhip.h)
-    _fields_ = [("img", ctypes.c_void_p), ("H", ctypes.c_int), ("W", ctypes.c_int), ("y0", ctypes.c_int),
-                ("x0", ctypes.c_int), ("mode", ctypes.c_int)]
+_PatchJob = struct("srhip_patch_job")
+_PatchJobF32 = struct("srhip_patch_job_f32")
+
+
+def _patch_gather(who, dtype, Job, tiles, ids, y0, x0, modes, P, out):
+    """patch_gather / patch_gather_f32: the job table of ``Job`` over tiles of ``dtype``, one launch of srhip_<who>"""
+    B = len(ids)
+    dev = tiles[ids[0]].device
+    if out is None:
+        out = torch.empty(B, 1, P, P, device=dev, dtype=torch.float32)
+    _chk(out)
+    jobs = (Job * B)()
+    for b in range(B):
+        t = tiles[ids[b]]
+        if not (t.is_cuda and t.dtype == dtype and t.dim() == 2 and t.is_contiguous()):
+            raise ValueError(f"{who}: tiles must be contiguous {str(dtype)[6:]} CUDA tensors [H, W]")
+        jobs[b].img, jobs[b].H, jobs[b].W = t.data_ptr(), t.shape[0], t.shape[1]
+        jobs[b].y0, jobs[b].x0, jobs[b].mode = int(y0[b]), int(x0[b]), int(modes[b])
+    call("srhip_" + who, ctypes.addressof(jobs), B, P, _p(out), _st())
+    return out
 
 
 def patch_gather(tiles, ids, y0, x0, modes, P, out=None):
     """[B,1,P,P] float32 batch out of device-resident uint8 tiles: crop at (y0, x0), augment_img mode 0..7,
     /255 -- the per-sample tail of DatasetDPSR.__getitem__ (dataset_dpsr.py:866-894,914-915).  ``tiles``:
     sequence of contiguous uint8 CUDA tensors [H, W]; ids / y0 / x0 / modes: per-sample Python ints."""
-    B = len(ids)
-    dev = tiles[ids[0]].device
-    if out is None:
-        out = torch.empty(B, 1, P, P, device=dev, dtype=torch.float32)
-    _chk(out)
-    jobs = (_PatchJob * B)()
-    for b in range(B):
-        t = tiles[ids[b]]
-        if not (t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and t.is_contiguous()):
-            raise ValueError("patch_gather: tiles must be contiguous uint8 CUDA tensors [H, W]")
-        jobs[b].img, jobs[b].H, jobs[b].W = t.data_ptr(), t.shape[0], t.shape[1]
-        jobs[b].y0, jobs[b].x0, jobs[b].mode = int(y0[b]), int(x0[b]), int(modes[b])
-    call("srhip_patch_gather", ctypes.addressof(jobs), B, P, _p(out), _st())
-    return out
-
-
-class _PatchJobF32(ctypes.Structure):   # srhip_patch_job_f32 (include/srhip.h)
-    _fields_ = [("img", ctypes.c_void_p), ("H", ctypes.c_int), ("W", ctypes.c_int), ("y0", ctypes.c_int),
-                ("x0", ctypes.c_int), ("mode", ctypes.c_int)]
+    return _patch_gather("patch_gather", torch.uint8, _PatchJob, tiles, ids, y0, x0, modes, P, out)
 
 
 def patch_gather_f32(tiles, ids, y0, x0, modes, P, out=None):
     """patch_gather out of device-resident FLOAT32 tiles (the low-resolution tiles of HR-only pairs, which stay the
     float image of util.imresize_np: dataset_dpsr.py:810,872-873,893): the same crop / augment_img mode / [B,1,P,P]
     layout, a pure copy."""
-    B = len(ids)
-    dev = tiles[ids[0]].device
-    if out is None:
-        out = torch.empty(B, 1, P, P, device=dev, dtype=torch.float32)
-    _chk(out)
-    jobs = (_PatchJobF32 * B)()
-    for b in range(B):
-        t = tiles[ids[b]]
-        if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous()):
-            raise ValueError("patch_gather_f32: tiles must be contiguous float32 CUDA tensors [H, W]")
-        jobs[b].img, jobs[b].H, jobs[b].W = t.data_ptr(), t.shape[0], t.shape[1]
-        jobs[b].y0, jobs[b].x0, jobs[b].mode = int(y0[b]), int(x0[b]), int(modes[b])
-    call("srhip_patch_gather_f32", ctypes.addressof(jobs), B, P, _p(out), _st())
-    return out
+    return _patch_gather("patch_gather_f32", torch.float32, _PatchJobF32, tiles, ids, y0, x0, modes, P, out)
 
 
 def imresize_aa(src, scale, out=None):
@@ -1875,8 +1882,7 @@ def resize_cubic(src, size_hw, out=None):
     return out
 
 
-class _PyrLevel(ctypes.Structure):   # srhip_pyr_level (include/srhip.h)
-    _fields_ = [("dst", ctypes.c_void_p), ("Ho", ctypes.c_int), ("Wo", ctypes.c_int)]
+_PyrLevel = struct("srhip_pyr_level")
 
 
 PYR_MAX_LEVELS = 8
@@ -1990,10 +1996,7 @@ def hist_u8(img):
     return counts
 
 
-class _OriginTile(ctypes.Structure):   # srhip_origin_tile (include/srhip.h)
-    _fields_ = [("img", ctypes.c_void_p), ("d2", ctypes.c_void_p), ("rowcum", ctypes.c_void_p), ("H", ctypes.c_int),
-                ("W", ctypes.c_int), ("threshold", ctypes.c_int), ("P", ctypes.c_int), ("style", ctypes.c_int),
-                ("pad_", ctypes.c_int)]
+_OriginTile = struct("srhip_origin_tile")
 
 
 ORIGIN_STYLES = {"roi": 0, "edt": 1, "edt*roi": 2}      # SRHIP_ORIGIN_*
@@ -2284,13 +2287,10 @@ def dsr_splines_bwd(xi, dy, table, order, meta, gtable, n_splines, in_ksz, n_hid
 
 
 # ------------------------------------------------------------------ test modes (tta.hip)
-class _ViewJob(ctypes.Structure):    # srhip_view_job (include/srhip.h)
-    _fields_ = [("y0", ctypes.c_int), ("x0", ctypes.c_int), ("h", ctypes.c_int), ("w", ctypes.c_int), ("mode", ctypes.c_int)]
+_ViewJob = struct("srhip_view_job")
 
 
-class _ViewDesc(ctypes.Structure):   # srhip_view_desc (include/srhip.h)
-    _fields_ = [("tiles", ctypes.c_void_p), ("mode", ctypes.c_int), ("depth", ctypes.c_int), ("th", ctypes.c_int),
-                ("tw", ctypes.c_int), ("h", ctypes.c_int * 9), ("w", ctypes.c_int * 9)]
+_ViewDesc = struct("srhip_view_desc")
 
 
 def _to_device_table(arr, device):

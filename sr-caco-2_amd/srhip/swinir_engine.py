@@ -17,6 +17,7 @@ backward = 4 data-gradient GEMMs + 4 weight-gradient GEMMs (+ slice reducers)
 import os
 
 import torch
+import torch.nn.functional as F
 
 from . import ops
 
@@ -41,6 +42,13 @@ class _Bufs:
         if self.d:
             ops.note_realloc()
         self.d.clear()
+
+
+def bicubic_clamped(x, scale):
+    """[B,1,h,w] -> [B,s*h,s*w]: the bicubic interpolation (align_corners False), clamped to [0, 1], in front of the nets
+    that refine an interpolated input (VDSR, DRRN, MemNet, DSR-Splines) -- stock PyTorch-ROCm, as in the reference."""
+    out = F.interpolate(x, size=(scale * x.shape[2], scale * x.shape[3]), mode='bicubic', align_corners=False)
+    return torch.clamp(out, min=0.0, max=1.0)[:, 0].contiguous()
 
 
 def net_dev(net):
@@ -205,9 +213,7 @@ class SwinIREngine:
                                biasG=D.get(f"{i}.biasG", b.num_heads, 64, 64, device=dev)
                                if ops.wattn_f16_ok(C, b.num_heads) else None)
             for name, conv in self._convs():
-                co, ci = conv.weight.shape[:2]
-                tb.conv(conv.weight.data, ws.planes(name + ".wp", 9 * co, ci, dev))
-                tb.conv(conv.weight.data, ws.planes(name + ".wpt", 9 * ci, co, dev), data_grad=True)
+                tb.conv_pair(name, conv.weight.data, ws)
             if self.conv3:
                 P = self.c4p
                 for name, _, _ in self._rconvs():
@@ -238,19 +244,14 @@ class SwinIREngine:
             ops.bias_expand(b.attn.relative_position_bias_table.data,
                             D.get(f"{i}.biasT", heads, 64, 64, device=dev),
                             D.get(f"{i}.biasN", heads, 64, 64, device=dev))
-        for name, conv in self._convs():
-            co, ci = conv.weight.shape[:2]
-            ops.pack_conv_weight(conv.weight.data, D.get(name + ".wp", 9, co, ci, device=dev),
-                                 D.get(name + ".wpt", 9, ci, co, device=dev))
         ws = self.ws
+        for name, conv in self._convs():
+            ws.pack_conv(name, conv.weight.data, D)
         for i, b in enumerate(self.blocks):
             for k in ("wq", "wqT", "wpT", "w1", "w1T", "w2T"):
                 ws.register(f"{i}.{k}", D.d[f"{i}.{k}"])
             ws.register(f"{i}.wproj", b.attn.proj.weight.data)
             ws.register(f"{i}.w2", b.mlp.fc2.weight.data)
-        for name, _ in self._convs():
-            ws.register(name + ".wp", D.d[name + ".wp"])
-            ws.register(name + ".wpt", D.d[name + ".wpt"])
         if self.conv3:
             P = self.c4p
             for name, _, _ in self._rconvs():

@@ -8,10 +8,9 @@ libsrhip kernel: the 1-channel edge convs of small.hip, the bf16x3 implicit-GEMM
 epilogue, the ReLU mask of the backward as the data-gradient conv's epilogue (epi 4).  NHWC throughout.
 """
 import torch
-import torch.nn.functional as F
 
 from . import ops
-from .swinir_engine import _Bufs
+from .swinir_engine import _Bufs, bicubic_clamped
 
 CH = 64
 
@@ -36,31 +35,11 @@ class VDSREngine:
         return [["conv1.", "trunk.", "conv2."]]
 
     def prepare(self):
-        D, ws = self.derived, self.ws
-        dev = self.net.conv2.weight.device
-        convs = [(f"t{k}", self.net.trunk[k].conv) for k in range(self.nt)]
-        if ws.use_bx3:
-            sig = tuple(p.data_ptr() for p in self.net.parameters())
-            if self._prep is None or sig != self._prep_sig:
-                tb = ops.PrepTable()
-                for name, conv in convs:
-                    tb.conv(conv.weight.data, ws.planes(name + ".wp", 9 * CH, CH, dev))
-                    tb.conv(conv.weight.data, ws.planes(name + ".wpt", 9 * CH, CH, dev), data_grad=True)
-                self._prep, self._prep_sig = tb.build(dev), sig
-            self._prep.run()
-        else:
-            for name, conv in convs:
-                ops.pack_conv_weight(conv.weight.data, D.get(name + ".wp", 9, CH, CH, device=dev),
-                                     D.get(name + ".wpt", 9, CH, CH, device=dev))
-                ws.register(name + ".wp", D.d[name + ".wp"])
-                ws.register(name + ".wpt", D.d[name + ".wpt"])
-        self.prepared = True
+        ops.prepare_conv_packs(self, ((f"t{k}", self.net.trunk[k].conv.weight.data, False) for k in range(self.nt)))
 
     def interpolate(self, x):
         """network_vdsr.py:78-90: [B,1,h,w] -> [B,s*h,s*w], bicubic (align_corners False), clamped."""
-        s = self.net.upscale
-        out = F.interpolate(x, size=(s * x.shape[2], s * x.shape[3]), mode='bicubic', align_corners=False)
-        return torch.clamp(out, min=0.0, max=1.0)[:, 0].contiguous()
+        return bicubic_clamped(x, self.net.upscale)
 
     def forward_h16(self, x):
         """--amp evaluation on fp16 storage (conv_h16.hip): the same launches with float16 feature maps, one fp16 product."""

@@ -58,6 +58,52 @@ def test_ctypes_structs_mirror_the_header(tmp_path):
         assert getattr(cls, last).offset == int(off), (name, last)
 
 
+HEADER_STRUCTS = ["srhip_prep_entry", "srhip_conv_wgrad_h16_item", "srhip_tn_problem", "srhip_reduce_problem", "srhip_pyr_level",
+                  "srhip_patch_job", "srhip_patch_job_f32", "srhip_origin_tile", "srhip_conv_wgrad_item", "srhip_view_job",
+                  "srhip_view_desc"]
+
+
+def test_every_struct_parsed_from_the_header_has_the_compilers_layout(tmp_path):
+    """_lib.parse_structs: as many structs as the header has ``typedef struct``, and of each one sizeof and the offsetof of
+    EVERY field as gcc reports them for the plain-C header."""
+    import ctypes
+    import re
+    from srhip import _lib, ops
+    structs = _lib.parse_structs()
+    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "srhip.h")).read(), flags=re.S)
+    assert len(structs) == len(re.findall(r"\btypedef\s+struct\b", text)) >= 11
+    assert set(HEADER_STRUCTS) <= set(structs)
+    assert all(_lib.struct(n)._fields_ == structs[n]._fields_ for n in structs)
+    assert ops._OriginTile is _lib.struct("srhip_origin_tile") and ops._TnProblem is _lib.struct("srhip_tn_problem")
+    body = "".join(f'  printf("{n} %zu", sizeof({n}));\n'
+                   + "".join(f'  printf(" %zu", offsetof({n}, {f[0]}));\n' for f in cls._fields_) + '  printf("\\n");\n'
+                   for n, cls in structs.items())
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "srhip.h"\nint main(void) {\n' + body + "  return 0;\n}\n")
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(tmp_path / "layout")], check=True)
+    lines = subprocess.run([str(tmp_path / "layout")], capture_output=True, text=True, check=True).stdout.strip().splitlines()
+    assert [line.split()[0] for line in lines] == list(structs)
+    for line in lines:
+        name, size, *offs = line.split()
+        cls = structs[name]
+        assert ctypes.sizeof(cls) == int(size), (name, ctypes.sizeof(cls), size)
+        assert [getattr(cls, f[0]).offset for f in cls._fields_] == [int(o) for o in offs], name
+    # what the parser reads beyond scalars: a pointer whatever it points to, an array, a comma list that shares the base type
+    assert dict(structs["srhip_view_desc"]._fields_)["h"] is ctypes.c_int * 9
+    assert dict(structs["srhip_patch_job"]._fields_) == dict(img=ctypes.c_void_p, H=ctypes.c_int, W=ctypes.c_int, y0=ctypes.c_int,
+                                                              x0=ctypes.c_int, mode=ctypes.c_int)
+    assert _lib.parse_structs("typedef struct { float *a, b; long n; } srhip_t;")["srhip_t"]._fields_ == \
+        [("a", ctypes.c_void_p), ("b", ctypes.c_float), ("n", ctypes.c_long)]
+
+
+@pytest.mark.parametrize("decl", ["unsigned long long x;", "struct { int a; float b; } s;", "int a : 3;", "void (*f)(int);"])
+def test_struct_parser_refuses_what_it_does_not_read(decl):
+    from srhip import _lib
+    with pytest.raises(ValueError, match="srhip_odd"):
+        _lib.parse_structs("typedef struct { int n; /* then */ " + decl + " float* p; } srhip_odd;\n")
+    assert list(_lib.parse_structs("typedef struct { int n; float* p; } srhip_odd;\n")) == ["srhip_odd"]
+
+
 # (S, part_floats) of the bx3 planners, recorded before the weight-gradient kernel forms were chosen in one place:
 # srhip_tn_plan_bx3 (M, NI, NJ, conv) at SwinIR's Linears and 180 -> 180 conv, EDSR's 64 -> 64 and 64 -> 256 (PixelShuffle)
 # convs at 8 x 64^2 / 128^2 / 256^2, DRRN's 128 -> 128 and ragged / narrow widths; srhip_conv3x3_wgrad_batched_plan
