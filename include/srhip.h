@@ -484,6 +484,13 @@ int srhip_clip01(float* x, long n, void* stream);
  * then columns).  src, tmp and dst must not overlap. */
 int srhip_imresize_aa(const void* src, int is_u8, float* tmp, float* dst, int B, int H, int W, int Ho, int Wo, double scale,
                       void* stream);
+/* srhip_imresize_aa on 16-BIT images: the rows pass reads a grey level v as np.float32(min(v, in_max) / float(in_max)),
+ * 1 <= in_max <= 65535 (srhip_patch_gather_u16's rule; util.uint162single, utils_image.py:330-331, at 65535), so the result
+ * is util.imresize_np (utils_image.py:1505-1578) of the full-depth float image, bit for bit: the LR image of an HR-only pair
+ * whose tile is 16-bit (dataset_dpsr.py:798-824).  Same weights, sums, tmp, refusals and columns pass; rows whose length is a
+ * multiple of 8 on 16-byte aligned buffers move as 16-byte accesses (8 pixels a load), others as scalars. */
+int srhip_imresize_aa_u16(const unsigned short* src, int in_max, float* tmp, float* dst, int B, int H, int W, int Ho, int Wo,
+                          double scale, void* stream);
 
 /* ---- the target pyramid of the multi-scale training losses, one launch (resize.hip) ------------------------------ */
 /* loss_prosr / loss_mslaprs (dlib/models/model_plain.py:257-264,298-305): every intermediate image is compared with
@@ -826,6 +833,23 @@ typedef struct {
   int H, W, y0, x0, mode;
 } srhip_patch_job_f32;
 int srhip_patch_gather_f32(const srhip_patch_job_f32* jobs, int B, int P, float* out, void* stream);
+/* The same crop / augment_img mode / [B][1][P][P] layout out of resident 16-BIT tiles, at full depth: a grey level v becomes
+ * np.float32(min(v, in_max) / float(in_max)), 1 <= in_max <= 65535 -- the quotient in double, rounded once; srhip_ingest_pad's
+ * rule, of which util.uint162single (dlib/utils/utils_image.py:330-331) is the case in_max = 65535 and 4095 serves 12-bit
+ * data in a 16-bit container.  The reference's cv2.imread(path, 0) (utils_image.py:237-243) reduces such a file to 8 bits
+ * before dataset_dpsr.py:866-894,914-915 see it; here the patch keeps every level.  The argument checks of
+ * srhip_patch_gather (mode, crop inside the tile, NULL image).  jobs is a HOST array; bit-exact. */
+typedef struct {
+  const unsigned short* img;  /* device pointer */
+  int H, W, y0, x0, mode;
+} srhip_patch_job_u16;
+int srhip_patch_gather_u16(const srhip_patch_job_u16* jobs, int B, int P, int in_max, float* out, void* stream);
+/* n resident 16-bit grey levels -> the 8-bit levels 0 .. 255 that the crop samplers (ROI image, Otsu's histogram,
+ * --sample_tr_patch_th: dataset_dpsr.py:330-457,479-480) and the metrics work on: dst = tensor2uint82float of the full-depth
+ * value (utils_image.py:369-372), round_half_even(clamp(x, 0, 1) * 255) with x = np.float32(min(v, in_max) / float(in_max))
+ * and ONE float32 product -- so a pixel is inside the samplers' ROI exactly when it is inside the ROI the metric sweep builds
+ * from the same tile.  One launch; bit-exact.  src and dst must not overlap. */
+int srhip_levels_u16_to_u8(const unsigned short* src, unsigned char* dst, long n, int in_max, void* stream);
 /* ROI-weighted patch origins, the 'roi' sampler of the training crops (PatchSampler._roi,
  * dataset_dpsr.py:330-369): origin (r, c) of the (H-P) x (W-P) candidates has probability
  * proportional to exp(5*roi) + 1, roi = img[r + P/2][c + P/2] >= threshold.  One uniform in [0,1)

@@ -5,6 +5,7 @@
 // :381-382 single2tensor3, :469-487 augment_img).  Index-only + one exact conversion:
 // bit-exact against the reference (np.float32(v / 255.): the division is done in float64).
 #include "common.h"
+#include "levels.h"
 #include "../../include/srhip.h"
 
 namespace {
@@ -56,6 +57,47 @@ __global__ void __launch_bounds__(256) k_patch_gather_f32(PatchJobsF32 jobs, int
     int si, sj;
     aug_src(J.mode, i, j, P, si, sj);
     o[idx] = J.img[(long)(J.y0 + si) * J.W + J.x0 + sj];
+  }
+}
+
+// The same crop / augmentation out of a resident 16-BIT tile, at full depth: np.float32(min(v, in_max) / float(in_max)), the
+// rule of srhip_ingest_pad (levels.h; util.uint162single, utils_image.py:330-331, is in_max = 65535).  Index-only + one exact
+// conversion: bit-exact.
+struct PatchJobsU16 {
+  struct J { const unsigned short* img; int W, y0, x0, mode; } j[MAXJOBS];
+};
+__global__ void __launch_bounds__(256) k_patch_gather_u16(PatchJobsU16 jobs, int P, unsigned in_max, float* __restrict__ out) {
+  const PatchJobsU16::J J = jobs.j[blockIdx.y];
+  float* o = out + (long)blockIdx.y * P * P;
+  const double dmax = (double)in_max;
+  for (int idx = blockIdx.x * 256 + threadIdx.x; idx < P * P; idx += gridDim.x * 256) {
+    const int i = idx / P, j = idx - i * P;
+    int si, sj;
+    aug_src(J.mode, i, j, P, si, sj);
+    o[idx] = unit_of(J.img[(long)(J.y0 + si) * J.W + J.x0 + sj], in_max, dmax);
+  }
+}
+
+// 16-bit grey levels -> the 8-bit levels the samplers and the metrics work on: tensor2uint82float of the full-depth value,
+// round_half_even(clamp(unit_of(v), 0, 1) * 255) (levels.h; utils_image.py:369-372).  Four pixels a thread: one 8-byte load and
+// one 4-byte store where both are aligned (vec), else -- and for the last n % 4 pixels -- pixel by pixel.
+typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
+typedef unsigned char u8x4 __attribute__((ext_vector_type(4)));
+__global__ void __launch_bounds__(256) k_levels_u16_to_u8(const unsigned short* __restrict__ src, unsigned char* __restrict__ dst,
+                                                          long n, unsigned in_max, int vec) {
+  const double dmax = (double)in_max;
+  const long groups = (n + 3) / 4;
+  for (long g = blockIdx.x * 256L + threadIdx.x; g < groups; g += (long)gridDim.x * 256) {
+    const long i = 4 * g;
+    if (vec && i + 3 < n) {
+      const u16x4 v = *(const u16x4*)(src + i);
+      *(u8x4*)(dst + i) = u8x4{(unsigned char)level_of(unit_of(v.x, in_max, dmax), 255.f),
+                               (unsigned char)level_of(unit_of(v.y, in_max, dmax), 255.f),
+                               (unsigned char)level_of(unit_of(v.z, in_max, dmax), 255.f),
+                               (unsigned char)level_of(unit_of(v.w, in_max, dmax), 255.f)};
+    } else {
+      for (long k = i; k < i + 4 && k < n; ++k) dst[k] = (unsigned char)level_of(unit_of(src[k], in_max, dmax), 255.f);
+    }
   }
 }
 
@@ -213,5 +255,44 @@ extern "C" int srhip_patch_gather_f32(const srhip_patch_job_f32* jobs, int B, in
     hipLaunchKernelGGL(k_patch_gather_f32, dim3(gx, nb), dim3(256), 0, st, pj, P, out + (long)b0 * P * P);
   }
   SR_LAUNCH_CHECK("patch_gather_f32");
+  return 0;
+}
+
+extern "C" int srhip_patch_gather_u16(const srhip_patch_job_u16* jobs, int B, int P, int in_max, float* out, void* stream) {
+  SR_REQUIRE(jobs && out && B > 0 && P > 0, "patch_gather_u16: empty batch / NULL argument");
+  SR_REQUIRE(in_max >= 1 && in_max <= 65535, "patch_gather_u16: 1 <= in_max <= 65535 (got %d)", in_max);
+  for (int b = 0; b < B; ++b) {
+    const srhip_patch_job_u16& q = jobs[b];
+    SR_REQUIRE(q.img != nullptr, "patch_gather_u16: job %d has no image", b);
+    SR_REQUIRE((((uintptr_t)q.img) & 1) == 0, "patch_gather_u16: job %d: misaligned image", b);
+    SR_REQUIRE(q.mode >= 0 && q.mode <= 7, "patch_gather_u16: job %d: augmentation mode %d (0..7)", b, q.mode);
+    SR_REQUIRE(q.y0 >= 0 && q.x0 >= 0 && q.y0 + P <= q.H && q.x0 + P <= q.W,
+               "patch_gather_u16: job %d: crop (%d,%d)+%d outside the %dx%d tile", b, q.y0, q.x0, P, q.H, q.W);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  for (int b0 = 0; b0 < B; b0 += MAXJOBS) {
+    const int nb = B - b0 < MAXJOBS ? B - b0 : MAXJOBS;
+    PatchJobsU16 pj;
+    for (int b = 0; b < nb; ++b) {
+      const srhip_patch_job_u16& q = jobs[b0 + b];
+      pj.j[b].img = q.img; pj.j[b].W = q.W; pj.j[b].y0 = q.y0; pj.j[b].x0 = q.x0; pj.j[b].mode = q.mode;
+    }
+    const int gx = sr_cdiv((long)P * P, 256) < 64 ? sr_cdiv((long)P * P, 256) : 64;
+    hipLaunchKernelGGL(k_patch_gather_u16, dim3(gx, nb), dim3(256), 0, st, pj, P, (unsigned)in_max, out + (long)b0 * P * P);
+  }
+  SR_LAUNCH_CHECK("patch_gather_u16");
+  return 0;
+}
+
+extern "C" int srhip_levels_u16_to_u8(const unsigned short* src, unsigned char* dst, long n, int in_max, void* stream) {
+  SR_REQUIRE(src && dst && n > 0, "levels_u16_to_u8: empty image / NULL argument");
+  SR_REQUIRE(in_max >= 1 && in_max <= 65535, "levels_u16_to_u8: 1 <= in_max <= 65535 (got %d)", in_max);
+  SR_REQUIRE((((uintptr_t)src) & 1) == 0, "levels_u16_to_u8: misaligned pointer");
+  SR_REQUIRE(sr_disjoint(src, n * 2, dst, n), "levels_u16_to_u8: dst overlaps src");
+  const int vec = (((uintptr_t)src) & 7) == 0 && (((uintptr_t)dst) & 3) == 0;
+  long g = ((n + 3) / 4 + 255) / 256;
+  if (g > 16384) g = 16384;
+  hipLaunchKernelGGL(k_levels_u16_to_u8, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, src, dst, n, (unsigned)in_max, vec);
+  SR_LAUNCH_CHECK("levels_u16_to_u8");
   return 0;
 }

@@ -10,6 +10,7 @@
 // element.  The integer side of a full group is one 4-byte (8-bit pages) or 8-byte (16-bit pages) access where that piece is
 // aligned, else four scalar ones.  Any width works, odd ones included.
 #include "common.h"
+#include "levels.h"
 
 namespace {
 
@@ -20,11 +21,6 @@ typedef u16 u16x4 __attribute__((ext_vector_type(4)));
 template <typename T> struct Vec4;
 template <> struct Vec4<u8> { typedef u8x4 type; };
 template <> struct Vec4<u16> { typedef u16x4 type; };
-
-// np.float32(min(v, in_max) / float(in_max)): the quotient in double, rounded once more to float32
-__device__ __forceinline__ float unit_of(unsigned v, unsigned in_max, double dmax) {
-  return (float)((double)min(v, in_max) / dmax);
-}
 
 // dst[b][i][j] = unit(src[b][ri(i)][rj(j)]), ri(i) = i < H ? i : 2H - 1 - i (row H + k is row H - 1 - k), rj alike: the
 // columns are reflected in the row-padded image, so the corner is flipped both ways.  G groups per row (see above).
@@ -62,12 +58,10 @@ __global__ __launch_bounds__(256) void k_ingest_pad(const T* __restrict__ src, f
   }
 }
 
-// round_half_even(clamp(x, 0, 1) * out_max): fmaxf / fminf drop a NaN operand, so NaN -> 0, -inf -> 0, +inf -> out_max; ONE
-// float32 product (there is nothing it could be contracted with); v_rndne_f32 rounds half to even; the result is an integer
-// in [0, 65535], exact in float32.
+// level_of (levels.h) with the non-finite flag
 __device__ __forceinline__ unsigned uint_of(float x, float out_max, int& bad) {
   bad |= !(fabsf(x) <= 3.402823466e+38f);                       // NaN or +-inf
-  return (unsigned)rintf(__fmul_rn(fminf(fmaxf(x, 0.f), 1.f), out_max));
+  return level_of(x, out_max);
 }
 
 // dst[b][i][j] = uint_of(x[b][i][j]) for i < Ho, j < Wo; the groups follow the alignment of x's rows (16-byte loads)

@@ -11,6 +11,7 @@
 // near-ties it may differ by one grey level); pinned bit-exact (uint8) / 1e-6 (float32) against oracle/cv2_cubic.py,
 // the same restatement in numpy.
 #include "common.h"
+#include "levels.h"
 #include "../../include/srhip.h"
 
 namespace {
@@ -289,6 +290,56 @@ __global__ void __launch_bounds__(256) k_imresize_aa_rows(const void* __restrict
   }
 }
 
+// The rows pass on a 16-BIT source, read at full depth by unit_of (levels.h): the same weights, tap order and f64 sums, so a
+// source of 257 v gives the bits of the uint8 kernel on v.  One thread per 8 consecutive columns: with VEC (whole runs per row,
+// 16-byte aligned src and tmp) a tap is ONE 16-byte load of 8 pixels and the result two 16-byte stores.
+constexpr int AA_RUN16 = 8;
+typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+
+template <bool VEC>
+__global__ void __launch_bounds__(256) k_imresize_aa_rows_u16(const unsigned short* __restrict__ src, float* __restrict__ tmp,
+                                                              int B, int H, int W, int Ho, double scale, int P, unsigned in_max) {
+#pragma clang fp contract(off)
+  const int runs = (W + AA_RUN16 - 1) / AA_RUN16;
+  const long item = blockIdx.x * 256L + threadIdx.x;
+  if (item >= (long)B * Ho * runs) return;
+  const int x0 = (int)(item % runs) * AA_RUN16;
+  const long row = item / runs;                 // b * Ho + oy
+  const int oy = (int)(row % Ho);
+  const long img = (row / Ho) * (long)H * W;
+  const double dmax = (double)in_max;
+  double u;
+  const int left = aa_left(oy, scale, u);
+  const double ws = aa_weight_sum(u, left, P, scale);
+  double acc[AA_RUN16] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int k = 0; k < P; ++k) {
+    const double w = aa_weight(u, left, k, scale) / ws;
+    if (w == 0.0) continue;                     // as k_imresize_aa_rows: never dereferenced
+    const int j = min(max(aa_index(left, k, H), 0), H - 1);
+    const unsigned short* p = src + img + (long)j * W + x0;
+    float v[AA_RUN16];
+    if (VEC) {
+      const u16x8 q = *(const u16x8*)p;
+#pragma unroll
+      for (int e = 0; e < AA_RUN16; ++e) v[e] = unit_of(q[e], in_max, dmax);
+    } else {
+#pragma unroll
+      for (int e = 0; e < AA_RUN16; ++e) v[e] = x0 + e < W ? unit_of(p[e], in_max, dmax) : 0.f;
+    }
+#pragma unroll
+    for (int e = 0; e < AA_RUN16; ++e) acc[e] += w * (double)v[e];
+  }
+  float* d = tmp + row * W + x0;
+  if (VEC) {
+    *(f32x4*)d = f32x4{(float)acc[0], (float)acc[1], (float)acc[2], (float)acc[3]};
+    *(f32x4*)(d + 4) = f32x4{(float)acc[4], (float)acc[5], (float)acc[6], (float)acc[7]};
+  } else {
+#pragma unroll
+    for (int e = 0; e < AA_RUN16; ++e)
+      if (x0 + e < W) d[e] = (float)acc[e];
+  }
+}
+
 template <bool VEC>
 __global__ void __launch_bounds__(256) k_imresize_aa_cols(const float* __restrict__ tmp, float* __restrict__ dst, long rows, int W,
                                                           int Wo, double scale, int P) {
@@ -395,8 +446,10 @@ int srhip_resize_bicubic_ac_pyramid(const float* src, int B, int H, int W, const
   return 0;
 }
 
-int srhip_imresize_aa(const void* src, int is_u8, float* tmp, float* dst, int B, int H, int W, int Ho, int Wo, double scale,
-                      void* stream) {
+// both entry points: es = bytes per source pixel (4 float32, 1 uint8, 2 uint16 read by in_max)
+static int imresize_aa_run(const void* src, int es, int in_max, float* tmp, float* dst, int B, int H, int W, int Ho, int Wo,
+                           double scale, void* stream) {
+  const bool is_u8 = es == 1;
   SR_REQUIRE(src && tmp && dst && B > 0 && H > 0 && W > 0, "imresize_aa: empty image / NULL argument");
   SR_REQUIRE(scale > 0.0 && scale < 1.0 && scale >= 1.0 / 64, "imresize_aa: scale %g (antialiased down-scaling: 1/64 <= scale < 1)",
              scale);
@@ -407,17 +460,23 @@ int srhip_imresize_aa(const void* src, int is_u8, float* tmp, float* dst, int B,
   SR_REQUIRE(P <= AA_MAXTAPS, "imresize_aa: %d taps (at most %d)", P, AA_MAXTAPS);
   SR_REQUIRE(aa_axis_fits(H, Ho, P, scale) && aa_axis_fits(W, Wo, P, scale),
              "imresize_aa: a %dx%d image is too small for scale %g: a tap would mirror past the opposite border", H, W, scale);
-  const long src_bytes = (long)B * H * W * (is_u8 ? 1 : 4), tmp_bytes = (long)B * Ho * W * 4, dst_bytes = (long)B * Ho * Wo * 4;
+  const long src_bytes = (long)B * H * W * es, tmp_bytes = (long)B * Ho * W * 4, dst_bytes = (long)B * Ho * Wo * 4;
   SR_REQUIRE(sr_disjoint(tmp, tmp_bytes, src, src_bytes) && sr_disjoint(dst, dst_bytes, src, src_bytes) &&
              sr_disjoint(dst, dst_bytes, tmp, tmp_bytes), "imresize_aa: src, tmp and dst overlap");
-  const long n1 = ((long)B * Ho * sr_cdiv(W, AA_RUN) + 255) / 256, n2 = ((long)B * Ho * sr_cdiv(Wo, AA_RUN) + 255) / 256;
+  const long n1 = ((long)B * Ho * sr_cdiv(W, es == 2 ? AA_RUN16 : AA_RUN) + 255) / 256;
+  const long n2 = ((long)B * Ho * sr_cdiv(Wo, AA_RUN) + 255) / 256;
   SR_REQUIRE(n1 < (1L << 31) && n2 < (1L << 31), "imresize_aa: too many pixels for one launch");
   hipStream_t st = (hipStream_t)stream;
   // 16-byte accesses where every row starts on one: whole runs per row and aligned bases (4 bytes for a uint8 source)
   const bool v1 = W % AA_RUN == 0 && ((uintptr_t)src & (is_u8 ? 3 : 15)) == 0 && ((uintptr_t)tmp & 15) == 0;
   const bool v2 = Wo % AA_RUN == 0 && ((uintptr_t)dst & 15) == 0;
   const dim3 g1((unsigned)n1), g2((unsigned)n2), blk(256);
-  if (is_u8) {
+  if (es == 2) {      // 8 pixels a thread: whole runs per row and 16-byte aligned bases
+    const bool v16 = W % AA_RUN16 == 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)tmp & 15) == 0;
+    const unsigned short* s16 = (const unsigned short*)src;
+    if (v16) hipLaunchKernelGGL(k_imresize_aa_rows_u16<true>, g1, blk, 0, st, s16, tmp, B, H, W, Ho, scale, P, (unsigned)in_max);
+    else hipLaunchKernelGGL(k_imresize_aa_rows_u16<false>, g1, blk, 0, st, s16, tmp, B, H, W, Ho, scale, P, (unsigned)in_max);
+  } else if (is_u8) {
     if (v1) hipLaunchKernelGGL((k_imresize_aa_rows<true, true>), g1, blk, 0, st, src, tmp, B, H, W, Ho, scale, P);
     else hipLaunchKernelGGL((k_imresize_aa_rows<true, false>), g1, blk, 0, st, src, tmp, B, H, W, Ho, scale, P);
   } else {
@@ -428,6 +487,18 @@ int srhip_imresize_aa(const void* src, int is_u8, float* tmp, float* dst, int B,
   else hipLaunchKernelGGL(k_imresize_aa_cols<false>, g2, blk, 0, st, (const float*)tmp, dst, (long)B * Ho, W, Wo, scale, P);
   SR_LAUNCH_CHECK("imresize_aa");
   return 0;
+}
+
+int srhip_imresize_aa(const void* src, int is_u8, float* tmp, float* dst, int B, int H, int W, int Ho, int Wo, double scale,
+                      void* stream) {
+  return imresize_aa_run(src, is_u8 ? 1 : 4, 0, tmp, dst, B, H, W, Ho, Wo, scale, stream);
+}
+
+int srhip_imresize_aa_u16(const unsigned short* src, int in_max, float* tmp, float* dst, int B, int H, int W, int Ho, int Wo,
+                          double scale, void* stream) {
+  SR_REQUIRE(in_max >= 1 && in_max <= 65535, "imresize_aa_u16: 1 <= in_max <= 65535 (got %d)", in_max);
+  SR_REQUIRE((((uintptr_t)src) & 1) == 0, "imresize_aa_u16: misaligned pointer");
+  return imresize_aa_run(src, 2, in_max, tmp, dst, B, H, W, Ho, Wo, scale, stream);
 }
 
 }  // extern "C"

@@ -207,7 +207,7 @@ def EvalPairsLike(args, pairs_h, pairs_l):
 
 
 class ResidentTrainSet:
-    """Training batches assembled ON the GPU from tiles that stay resident in HBM (uint8; float32 LR tiles of HR-only pairs) (a CACO-2
+    """Training batches assembled ON the GPU from tiles that stay resident in HBM (uint8, or uint16 at full depth; float32 LR tiles of HR-only pairs) (a CACO-2
     split is a few hundred 8-bit tiles: tens of MB against 288 GB) -- the MI355X form of the TRAIN phase of
     DatasetDPSR.__getitem__ + DataLoader (dataset_dpsr.py:746-757,826-947, utils_dataloaders.py:138-158) for
     sets that ship true low-resolution tiles:
@@ -237,12 +237,18 @@ class ResidentTrainSet:
       * the LR-only augmentations (--da_blur / --da_dot_bin_noise / --da_add_gaus_noise, :899-905) run on the host on
         the B low-resolution patches (a few hundred pixels each) with the reference's numpy stream, then l_to_h_img is
         resized from the augmented patch on the device and clipped (:905-906);
+      * 16-bit tiles (PIL mode I;16; the reference's cv2.imread(path, 0) would reduce them to 8 bits) stay resident as uint16
+        and reach the batch at full depth, np.float32(min(v, in_max) / in_max) with --in_max (65535; 4095 for 12-bit data):
+        srhip_patch_gather_u16, and srhip_imresize_aa_u16 for the float LR tile of an HR-only pair.  Where grey levels 0 .. 255
+        are needed -- the ROI image, Otsu's histogram, --sample_tr_patch_th -- a 16-bit LR tile is reduced once by
+        srhip_levels_u16_to_u8 to the levels of the metrics' ROI.  A set and a pair may mix depths.  Refused by name with a
+        16-bit tile: --ppiw, SRCNN, DSR-Splines, and a CACO-2 tile without a true LR tile;
       * --ppiw: per-colour weights from the split's HR histogram (:592-645), per-pixel lookup on the device (:1037-1056)."""
 
     def __init__(self, args, pairs_h: dict, pairs_l: dict, device, rank: int = 0, world: int = 1):
         import torch
         import torch.nn.functional as F
-        from dlib.utils.utils_dataloaders import imread_gray_uint8, ShardedSampler
+        from dlib.utils.utils_dataloaders import imread_gray, check_in_max, refuse_16bit, ShardedSampler
         from dlib.datasets import lowres
         if getattr(args, 'augment', False):
             raise NotImplementedError("ResidentTrainSet: --augment (the reference drops it too: dataset_dpsr.py:860-862 'passed')")
@@ -269,10 +275,13 @@ class ResidentTrainSet:
             raise AssertionError(f"{style} (sample_tr_patch: a pair whose low-resolution image is synthesised from a tile "
                                  f"that is not a CACO-2 tile is cropped uniformly only; first: "
                                  f"{self.ids_h[self.hr_only.index(True)]})")
+        self.in_max = check_in_max(getattr(args, 'in_max', None))           # the white level of 16-bit tiles (--in_max)
         hr_host = []
         for idx, (hk, lk) in enumerate(zip(self.ids_h, self.ids_l)):
             h_path = pairs_h[hk]['abs_path']
-            h_full = imread_gray_uint8(h_path)
+            h_full = imread_gray(h_path)                                    # uint8, or uint16 at full depth
+            if h_full.dtype == np.uint16:
+                refuse_16bit(args, hk)
             h = torch.from_numpy(h_full[:, :, 0].copy())
             hh, ww = h.shape[0] - h.shape[0] % self.sf, h.shape[1] - h.shape[1] % self.sf      # modcrop
             h = h[:hh, :ww].contiguous()
@@ -280,6 +289,8 @@ class ResidentTrainSet:
                 l = ev.low_res_f32(h_full[:hh, :ww], self.device).contiguous()
             else:
                 l_np, _ = ev.low_res_u8(idx, h_full, h_path)              # true tile, or the reference's synthesis
+                if l_np.dtype == np.uint16:
+                    refuse_16bit(args, lk)
                 l = torch.from_numpy(np.array(l_np[:, :, 0], copy=True))
                 l = l[:hh // self.sf, :ww // self.sf].contiguous()
             assert l.shape == (hh // self.sf, ww // self.sf), (hk, tuple(h.shape), tuple(l.shape))
@@ -288,7 +299,11 @@ class ResidentTrainSet:
             self.lr.append(l.to(self.device))
             hr_host.append(h.numpy())
             if style != SAMPLE_UNIF:      # the image the reference thresholds: cv2.resize(LR, HR size, INTER_CUBIC) (:813-821,852-857)
-                self.roi_src.append(lowres.l_to_h(self.lr[-1][None], (hh, ww))[0].contiguous())
+                roi_l = self.lr[-1]
+                if roi_l.dtype == torch.uint16:       # at the 8-bit levels of the metrics' ROI, reduced once
+                    from srhip import ops
+                    roi_l = ops.levels_u16_to_u8(roi_l, self.in_max)
+                self.roi_src.append(lowres.l_to_h(roi_l[None], (hh, ww))[0].contiguous())
         self.roi_host = [t.cpu().numpy() for t in self.roi_src] if self.host_sampler is not None else None
         if self.device_roi:
             self.roi = DeviceRoiSampler(self.roi_src, self.psize, int(args.sample_tr_patch_th), seed=int(args.myseed or 0) + rank)
@@ -329,7 +344,7 @@ class ResidentTrainSet:
                        for b, i in enumerate(ids)]
             modes = torch.randint(0, 8, (B,), device=self.device, generator=self.gen).cpu().tolist()
             y0, x0 = [o[0] for o in org], [o[1] for o in org]
-            batch = ops.train_batch(self.hr, self.lr, ids, y0, x0, modes, P, sf)
+            batch = ops.train_batch(self.hr, self.lr, ids, y0, x0, modes, P, sf, in_max=self.in_max)
             if self.da:       # LR-only augmentations (:899-905): B patches of (P / s)^2 pixels through the reference's numpy code
                 from dlib.datasets import lowres
                 host = batch['l_im'].permute(0, 2, 3, 1).cpu().numpy()

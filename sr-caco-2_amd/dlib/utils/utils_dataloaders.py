@@ -124,6 +124,58 @@ def imread_gray_uint8(path: str) -> np.ndarray:
     return a[:, :, None]
 
 
+def imread_gray(path: str) -> np.ndarray:
+    """A single-channel TIFF / PNG tile at the depth the file holds: HxWx1 uint8 for PIL modes L / P / 1 (as
+    imread_gray_uint8), HxWx1 uint16 in native byte order for I;16 and the byte-swapped I;16B.  The reference's
+    cv2.imread(path, 0) (utils_image.py:237-243) silently reduces a 16-bit file to 8 bits; this reader keeps every level,
+    and what follows reads it as np.float32(min(v, in_max) / in_max) (--in_max).  32-bit integer (I), float (F) and colour
+    files are refused by name: there is no rule for their range, and a colour tile is not what this pipeline trains on."""
+    from PIL import Image
+    with Image.open(path) as im:
+        if im.mode in ('L', 'P', '1'):
+            return np.asarray(im, dtype=np.uint8)[:, :, None]
+        if im.mode in ('I;16', 'I;16L', 'I;16B', 'I;16N'):
+            return np.ascontiguousarray(np.asarray(im).astype(np.uint16, copy=False))[:, :, None]
+        if im.mode in ('I', 'F'):
+            raise NotImplementedError(f"{path}: mode {im.mode!r} (32-bit {'integer' if im.mode == 'I' else 'float'}) image; "
+                                      f"tiles are 8-bit ('L') or 16-bit ('I;16') grey images")
+        raise NotImplementedError(f"{path}: mode {im.mode!r} (colour) image; tiles are 8-bit ('L') or 16-bit ('I;16') grey "
+                                  f"images")
+
+
+def check_in_max(in_max):
+    """--in_max: the white level of 16-bit tiles, 1 .. 65535 (None: 65535); no effect on 8-bit tiles"""
+    if in_max is None:
+        return 65535
+    if isinstance(in_max, bool) or int(in_max) != in_max or not 1 <= in_max <= 65535:
+        raise ValueError(f'--in_max {in_max}: the white level of 16-bit tiles is an integer in 1 .. 65535')
+    return int(in_max)
+
+
+def refuse_16bit(args, tile):
+    """what a set with a 16-bit tile cannot do, by name: raised when the set is built, before any training step"""
+    if getattr(args, 'ppiw', False):
+        raise NotImplementedError(f"--ppiw on a set with a 16-bit tile ({tile}): its per-colour table and its truncating "
+                                  f"lookup are defined on 256 grey levels")
+    net = (getattr(args, 'netG', None) or {}).get('net_type', getattr(args, 'net_type', None))
+    if net == constants.SRCNN:
+        raise NotImplementedError(f"{constants.SRCNN} takes 8-bit tiles only ({tile} is 16-bit): its input 'l_to_h_img' is "
+                                  f"cv2's fixed-point cubic interpolation of a uint8 image")
+    if net == constants.DSRSPLINES:
+        raise NotImplementedError(f"{constants.DSRSPLINES} takes 8-bit tiles only ({tile} is 16-bit): it holds one spline "
+                                  f"net per grey level 0 .. 255")
+
+
+def unit_of_levels(img: np.ndarray, in_max=None) -> np.ndarray:
+    """grey levels -> float32 in [0, 1]: uint8 / 255 (util.uint2single, utils_image.py:322-323); uint16 by the white level,
+    np.float32(min(v, in_max) / float(in_max)) (util.uint162single, :330-331, at 65535) -- the quotient in double, rounded once"""
+    if img.dtype == np.uint8:
+        return np.float32(img / 255.)
+    assert img.dtype == np.uint16, img.dtype
+    m = check_in_max(in_max)
+    return np.float32(np.minimum(img, m) / float(m))
+
+
 class EvalPairs:
     """EVAL-phase items of DatasetDPSR: per index the dict the evaluation loop consumes (dataset_dpsr.py:746-838,948-1005)
     with l_im / h_im / l_to_h_img float32 CHW in [0,1] = uint8 / 255 (utils_image.py:322-323,381-382).
@@ -138,12 +190,18 @@ class EvalPairs:
     srhip_resize_cubic on the device; for an HR-only pair its source is uint8(trunc(clamp(l_im * color_max, 0, 255))).  The
     reference truncates with ``astype(np.uint8)`` WITHOUT the clamp (:817): outside [0, 255] that conversion wraps or is
     undefined (a sharp 0/1 edge down-scaled by 2 reaches -0.04 .. 1.07), so this build clamps first; inside the range the
-    two agree."""
+    two agree.
+
+    16-bit tiles (imread_gray) keep their depth: h_im and a true 16-bit l_im are np.float32(min(v, in_max) / in_max)
+    (--in_max, unit_of_levels), the LR image of an HR-only 16-bit pair is srhip_imresize_aa_u16 of the tile, and -- no uint8 LR
+    image exists for such a pair -- 'l_to_h_img' is srhip_resize_cubic's FLOAT path on l_im, clipped to [0, 1], as the training
+    batches make it (:905-907).  'h_bits' (8 | 16) tells the evaluation loop at which depth to save a preview."""
 
     def __init__(self, args, pairs_h: dict, pairs_l: dict):
         self.args, self.pairs_h, self.pairs_l = args, pairs_h, pairs_l
         self.im_h_ids = list(pairs_h.keys())
         self.sf = args.scale
+        self.in_max = check_in_max(getattr(args, 'in_max', None))       # the white level of 16-bit tiles (--in_max)
         # ids <-> floats (dataset_dpsr.py:583-590): per-image details travel through all_gather as floats
         self.im_h_ids_to_float = {k: float(i) for i, k in enumerate(self.im_h_ids)}
         self.float_to_im_h_ids = {v: k for k, v in self.im_h_ids_to_float.items()}
@@ -166,28 +224,34 @@ class EvalPairs:
         return self._true_low_path(index) is None and not lowres.is_caco2(h_path)
 
     def low_res_f32(self, img_h: np.ndarray, device=None):
-        """util.imresize_np(uint2single(img_h), 1 / sf, True) of a MOD-CROPPED HR tile (uint8 HxWx1), float32 and neither
-        quantised nor clipped: a [h, w] tensor on ``device`` from srhip_imresize_aa, or -- device None -- an hxwx1 numpy
-        array from the host function (the path of a machine without a GPU)."""
-        assert img_h.dtype == np.uint8 and img_h.ndim == 3 and img_h.shape[2] == 1, (img_h.dtype, img_h.shape)
+        """util.imresize_np(uint2single(img_h), 1 / sf, True) of a MOD-CROPPED HR tile (uint8 or uint16 HxWx1; a 16-bit tile is
+        read by --in_max, unit_of_levels), float32 and neither quantised nor clipped: a [h, w] tensor on ``device`` from
+        srhip_imresize_aa / srhip_imresize_aa_u16, or -- device None -- an hxwx1 numpy array from the host function (the path
+        of a machine without a GPU)."""
+        assert img_h.dtype in (np.uint8, np.uint16) and img_h.ndim == 3 and img_h.shape[2] == 1, (img_h.dtype, img_h.shape)
         if device is None:
             from dlib.utils.utils_image import imresize_np
-            return imresize_np(np.float32(img_h / 255.), 1 / self.sf, True)
+            return imresize_np(unit_of_levels(img_h, self.in_max), 1 / self.sf, True)
         import torch
         from srhip import ops
         tile = torch.from_numpy(np.array(img_h[:, :, 0], copy=True))[None].to(device)
-        return ops.imresize_aa(tile, 1 / self.sf)[0]
+        return ops.imresize_aa(tile, 1 / self.sf, in_max=self.in_max)[0]
 
     def low_res_u8(self, index: int, img_h: np.ndarray, h_path: str):
-        """(LR tile uint8 HWC, its path): the true tile, or the reference's synthesis for a CACO-2 tile (:776-804).  The
-        pairs of an HR-only set (is_hr_only) have a float LR image: low_res_f32."""
+        """(LR tile HWC, its path): the true tile at the depth its file holds (uint8 or uint16), or the reference's synthesis
+        for a CACO-2 tile (:776-804; uint8, defined on uint8 tiles only).  The pairs of an HR-only set (is_hr_only) have a
+        float LR image: low_res_f32."""
         from dlib.datasets import lowres
         h_id = self.im_h_ids[index]
         l_path = self._true_low_path(index)
         if l_path is not None:
-            return imread_gray_uint8(l_path), l_path
+            return imread_gray(l_path), l_path
         if not lowres.is_caco2(h_path):
             raise ValueError(f'{h_id}: the low-resolution image of an HR-only pair is float32 (low_res_f32), not a uint8 tile')
+        if img_h.dtype != np.uint8:
+            raise NotImplementedError(f'{h_id}: a 16-bit CACO-2 tile without a true low-resolution tile: the synthesis of its '
+                                      f'low-resolution image (use_interpolated_low / inter_low_th, dataset_dpsr.py:776-804) is '
+                                      f'defined on uint8 tiles')
         cmin, cmax = getattr(self.args, 'color_min', 0), getattr(self.args, 'color_max', 255)
         lo = lowres.interpolate_torch(img_h, 1. / self.sf, getattr(self.args, 'basic_interpolation', 'bicubic'), cmin, cmax)
         lo = np.clip(lo, a_min=cmin, a_max=cmax)
@@ -201,31 +265,40 @@ class EvalPairs:
         h_id = self.im_h_ids[index]
         l_id = self.pairs_h[h_id]['low_path_key']
         h_path = self.pairs_h[h_id]['abs_path']
-        img_h_full = imread_gray_uint8(h_path)
+        img_h_full = imread_gray(h_path)
         hh, ww = img_h_full.shape[:2]
         img_h = img_h_full[:hh - hh % self.sf, :ww - ww % self.sf]            # modcrop (utils_image.py:295-306)
-        to_t = lambda a: torch.from_numpy(np.ascontiguousarray(np.float32(a / 255.))).permute(2, 0, 1).float()
+        to_t = lambda a: torch.from_numpy(np.ascontiguousarray(unit_of_levels(a, self.in_max))).permute(2, 0, 1).float()
         gpu = torch.cuda.is_available()
+        deep = img_h.dtype == np.uint16       # the float32 images keep the levels of a 16-bit pair: no uint8 LR image exists
         if self.is_hr_only(index):                   # imresize_np of the mod-cropped tile, kept in float32 (:777,810-813)
             if gpu:
                 l_dev = self.low_res_f32(img_h, 'cuda')
                 l_t = l_dev[None].cpu()
                 cmax = getattr(self.args, 'color_max', None)
                 cmax = 255. if cmax is None else float(cmax)
-                lu8 = (l_dev * cmax).clamp_(0., 255.).to(torch.uint8)[None]     # (img_l * color_max).astype(np.uint8) (:817)
+                if not deep:
+                    lu8 = (l_dev * cmax).clamp_(0., 255.).to(torch.uint8)[None]     # (img_l * color_max).astype(np.uint8) (:817)
             else:
                 l_t = torch.from_numpy(self.low_res_f32(img_h)).permute(2, 0, 1).contiguous()
             l_path = h_path
         else:
             img_l, l_path = self.low_res_u8(index, img_h_full, h_path)  # the synthesis sees the un-cropped tile (:752-760)
             l_t = to_t(img_l)
-            if gpu:
+            deep = deep or img_l.dtype == np.uint16
+            if gpu and not deep:
                 lu8 = torch.from_numpy(np.array(img_l[:, :, 0], copy=True))[None].cuda()
-        out = {'l_im': l_t, 'l_id': l_id, 'l_path': l_path, 'h_im': to_t(img_h), 'h_id': h_id, 'h_path': h_path}
+        if deep:
+            refuse_16bit(self.args, h_id)
+        out = {'l_im': l_t, 'l_id': l_id, 'l_path': l_path, 'h_im': to_t(img_h), 'h_id': h_id, 'h_path': h_path,
+               'h_bits': 8 * img_h.dtype.itemsize}
         if gpu:
             from srhip import ops
-            up = lowres.l_to_h(lu8, img_h.shape[:2])                     # cv2.resize(img_l, (W, H), INTER_CUBIC) (:813-821,836)
-            out['l_to_h_img'] = ops.u8_to_unit(up)                       # [1, H, W] float32 on the device
+            if deep:        # cv2.resize(INTER_CUBIC) of the float LR image, clipped, as the training batches' (:905-907)
+                out['l_to_h_img'] = ops.clip01_(lowres.l_to_h(l_t.cuda().contiguous(), img_h.shape[:2]))
+            else:
+                up = lowres.l_to_h(lu8, img_h.shape[:2])                 # cv2.resize(img_l, (W, H), INTER_CUBIC) (:813-821,836)
+                out['l_to_h_img'] = ops.u8_to_unit(up)                   # [1, H, W] float32 on the device
             out['l_to_h_img_aug'] = out['l_to_h_img']
         return out
 

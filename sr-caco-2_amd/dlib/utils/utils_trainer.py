@@ -142,6 +142,14 @@ def _save_prediction_png(e_u8: torch.Tensor, path: str):
     Image.fromarray(e_u8.squeeze().clamp(0, 255).to(torch.uint8).cpu().numpy().astype(np.uint8)).save(path)
 
 
+def _save_prediction_png16(e: torch.Tensor, path: str):
+    """e float32 [H, W] on the device -> an I;16 PNG of round_half_even(clamp(e, 0, 1) * 65535) (util.single2uint16,
+    utils_image.py:334-335; srhip_emit_uint): what predict.py --out_dtype uint16 writes"""
+    from PIL import Image
+    from srhip import ops
+    Image.fromarray(ops.emit_uint(e, 16, e.shape[-2], e.shape[-1]).cpu().numpy()).save(path)
+
+
 def _fast_update_tracker(args, tracker, mtr_val, split, ds_name, idx_best=None):
     """master metric first (it fixes the index of the best evaluation), the others follow
     (utils_trainer.py:764-798)."""
@@ -196,8 +204,12 @@ def fast_eval(model, data_loader, ds_name: str, split: str, tracker: dict, roi_t
             if with_roi:
                 roi_details[img_id] = {m: host[m][i, 1:].mean().item() for m in _MTRS}
             if seen + i < nbr_to_plot and getattr(args, 'is_master', True) and save_img_dir:
-                e_u8 = metrics.tensor2uint82float(vis['E'][i:i + 1].float().contiguous())
-                _save_prediction_png(e_u8, join(save_img_dir, f'{reformat_id(img_id)}.png'))
+                path = join(save_img_dir, f'{reformat_id(img_id)}.png')
+                if test_data.get('h_bits', [8] * (i + 1))[i] == 16:       # a 16-bit pair: the preview keeps the depth (I;16)
+                    _save_prediction_png16(vis['E'][i, 0].float().contiguous(), path)
+                else:
+                    e_u8 = metrics.tensor2uint82float(vis['E'][i:i + 1].float().contiguous())
+                    _save_prediction_png(e_u8, path)
         seen += test_data['l_im'].shape[0]
     n = float(seen)
     if getattr(args, 'distributed', False) and args.eval_bsize > 1:      # rank-sharded evaluation

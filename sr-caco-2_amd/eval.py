@@ -3,7 +3,7 @@
 (eval.py:46-146) on the libsrhip path:
 
     python eval.py --cudaid 0 --exp_path <folder> [--data_root <datasets>] [--splits_root <folds>]
-                   [--test_mode {0..4} [--test_refield 32] [--test_min_size 256]]
+                   [--test_mode {0..4} [--test_refield 32] [--test_min_size 256]] [--in_max N]
 
 <folder> is a reference-format experiment directory: ``config_model.yml`` (the yaml dump of the
 run's args, utils_parser.py:1397-1401) and ``best-models/G-model.pth`` (raw ``state_dict``,
@@ -38,8 +38,8 @@ from dlib.utils.utils_trainer import evaluate  # noqa: E402
 from dlib.utils.utils_tracker import find_last_tracker, save_tracker  # noqa: E402
 
 
-def evaluate_pretrained(argv=None):
-    t0 = dt.datetime.now()
+def load_args(argv=None):
+    """(command line, the experiment's configuration with the command line's overrides); no device use"""
     ap = argparse.ArgumentParser()
     ap.add_argument("--cudaid", type=str, default=None, help="cuda id.")
     ap.add_argument("--exp_path", type=str, default=None)
@@ -50,12 +50,19 @@ def evaluate_pretrained(argv=None):
                          "3 x8 self-ensemble, 4 split and x8")
     ap.add_argument("--test_refield", type=int, default=32, help="--test_mode 2 / 4: receptive field of the net")
     ap.add_argument("--test_min_size", type=int, default=256, help="--test_mode 2 / 4: up to min_size^2 pixels go in whole")
+    ap.add_argument("--in_max", type=int, default=None,
+                    help="white level of 16-bit tiles, 1 .. 65535 (default: the one the run recorded in config_model.yml, "
+                         "else 65535); no effect on 8-bit tiles")
     ns = ap.parse_args(argv)
+    if ns.in_max is not None and not 1 <= ns.in_max <= 65535:
+        ap.error(f"--in_max {ns.in_max}: the white level of 16-bit tiles is an integer in 1 .. 65535")
     exp_path = ns.exp_path
     assert exp_path and isdir(exp_path), exp_path
     with open(join(exp_path, 'config_model.yml'), 'r') as fy:
         args = Dict2Obj(yaml.safe_load(fy))
     args.distributed = False
+    if ns.in_max is not None:
+        args.in_max = ns.in_max
     if ns.data_root is None:
         raise SystemExit("eval.py: give --data_root (or SRHIP_DATA_ROOT): the parent of the dataset folders")
     args.data_root = ns.data_root
@@ -63,6 +70,13 @@ def evaluate_pretrained(argv=None):
         args.splits_root = ns.splits_root
     elif not os.path.isabs(args.splits_root or ''):
         args.splits_root = join(dirname(HERE), args.splits_root or 'folds')
+    return ns, args
+
+
+def evaluate_pretrained(argv=None):
+    t0 = dt.datetime.now()
+    ns, args = load_args(argv)
+    exp_path = ns.exp_path
     args.outd = exp_path
     split = args.test_dsets
     assert len(split.split(constants.SEP)) == 1, split

@@ -176,6 +176,10 @@ def parse_input(argv=None):
               'da_dot_bin_noise_prob', 'da_dot_bin_noise_area', 'da_dot_bin_noise_p', 'da_add_gaus_noise_prob',
               'da_add_gaus_noise_area', 'da_add_gaus_noise_std'):
         ap.add_argument(f'--{k}', type=float, default=None)
+    # (not a reference option) the white level of 16-bit tiles, which are read as min(v, in_max) / in_max: 65535 when not
+    # given, 4095 for 12-bit data in a 16-bit container; no effect on 8-bit tiles.  A key of the configuration -- and of
+    # config_model.yml, where eval.py and predict.py find it -- only when given.
+    ap.add_argument('--in_max', type=int, default=None)
     ap.add_argument('--init_pretrained_path', type=str, default=None)        # netG['init_pretrained_path'] (utils_config.py:146)
     for k, t in IGNORED_FLAGS.items():
         if k not in cfg['train']:
@@ -232,6 +236,8 @@ def parse_input(argv=None):
         if v is not None and dflt is not None and v != dflt:
             ap.error(f"--{k} {v}: this option changes what the run computes and is not implemented on this path "
                      f"(only the reference's default {dflt!r} is accepted)")
+    if ns.in_max is not None and not 1 <= ns.in_max <= 65535:
+        ap.error(f"--in_max {ns.in_max}: the white level of 16-bit tiles is an integer in 1 .. 65535")
     # any non-None CLI value overrides the top-level / nested key (utils_parser.py:900-923)
     skip = set(IGNORED_FLAGS) | set(DEFAULT_ONLY_FLAGS) | {f'{nt}_{k}' for k in init_defaults} | {'init_pretrained_path'}
     for k, v in vars(ns).items():

@@ -1815,10 +1815,12 @@ def loss_stencil(pred, target, kind, lam=1.0, norm=2, ksz=3, channel_norm=False,
 # ------------------------------------------------------------------ input pipeline (f2)
 _PatchJob = struct("srhip_patch_job")
 _PatchJobF32 = struct("srhip_patch_job_f32")
+_PatchJobU16 = struct("srhip_patch_job_u16")
 
 
-def _patch_gather(who, dtype, Job, tiles, ids, y0, x0, modes, P, out):
-    """patch_gather / patch_gather_f32: the job table of ``Job`` over tiles of ``dtype``, one launch of srhip_<who>"""
+def _patch_gather(who, dtype, Job, tiles, ids, y0, x0, modes, P, out, *extra):
+    """patch_gather / patch_gather_f32 / patch_gather_u16: the job table of ``Job`` over tiles of ``dtype``, one launch of
+    srhip_<who>; ``extra``: the arguments between P and out (in_max)"""
     B = len(ids)
     dev = tiles[ids[0]].device
     if out is None:
@@ -1831,7 +1833,7 @@ def _patch_gather(who, dtype, Job, tiles, ids, y0, x0, modes, P, out):
             raise ValueError(f"{who}: tiles must be contiguous {str(dtype)[6:]} CUDA tensors [H, W]")
         jobs[b].img, jobs[b].H, jobs[b].W = t.data_ptr(), t.shape[0], t.shape[1]
         jobs[b].y0, jobs[b].x0, jobs[b].mode = int(y0[b]), int(x0[b]), int(modes[b])
-    call("srhip_" + who, ctypes.addressof(jobs), B, P, _p(out), _st())
+    call("srhip_" + who, ctypes.addressof(jobs), B, P, *extra, _p(out), _st())
     return out
 
 
@@ -1849,13 +1851,44 @@ def patch_gather_f32(tiles, ids, y0, x0, modes, P, out=None):
     return _patch_gather("patch_gather_f32", torch.float32, _PatchJobF32, tiles, ids, y0, x0, modes, P, out)
 
 
-def imresize_aa(src, scale, out=None):
+def _in_max(in_max, who):
+    """the white level of 16-bit grey levels: 65535 when None"""
+    in_max = 65535 if in_max is None else in_max
+    if int(in_max) != in_max or not 1 <= in_max <= 65535:
+        raise ValueError(f"{who}: in_max {in_max} is outside 1 .. 65535")
+    return int(in_max)
+
+
+def patch_gather_u16(tiles, ids, y0, x0, modes, P, in_max=None, out=None):
+    """patch_gather out of device-resident UINT16 tiles at full depth: a grey level v becomes
+    np.float32(min(v, in_max) / float(in_max)) (ingest_pad's rule; in_max None = 65535, util.uint162single); the same crop /
+    augment_img mode / [B,1,P,P] layout."""
+    return _patch_gather("patch_gather_u16", torch.uint16, _PatchJobU16, tiles, ids, y0, x0, modes, P, out,
+                         _in_max(in_max, "patch_gather_u16"))
+
+
+def levels_u16_to_u8(src, in_max=None, out=None):
+    """uint16 grey levels (any shape) -> the uint8 levels 0 .. 255 of tensor2uint82float on the full-depth value:
+    round_half_even(np.float32(min(v, in_max) / float(in_max)) * 255) -- the image the crop samplers threshold.  One launch."""
+    if not (torch.is_tensor(src) and src.is_cuda and src.dtype == torch.uint16 and src.is_contiguous() and src.numel() > 0):
+        raise ValueError("levels_u16_to_u8: src must be a contiguous, non-empty uint16 CUDA tensor")
+    if out is None:
+        out = torch.empty(src.shape, dtype=torch.uint8, device=src.device)
+    elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == src.numel()):
+        raise ValueError("levels_u16_to_u8: out must be a contiguous uint8 CUDA tensor of src's size")
+    call("srhip_levels_u16_to_u8", _p(src), _p(out), src.numel(), _in_max(in_max, "levels_u16_to_u8"), _st())
+    return out
+
+
+def imresize_aa(src, scale, out=None, in_max=None):
     """util.imresize_np(img, scale, antialiasing=True) for scale < 1 on a batch of 1-channel images [B, H, W], uint8 (read
-    as v / 255) or float32 -> float32 [B, ceil(H * scale), ceil(W * scale)]: the MATLAB-style antialiased bicubic
-    down-scaling behind the low-resolution image of an HR-only pair (resize.hip; utils_image.py:1358-1422,1505-1578)."""
+    as v / 255), uint16 (read as min(v, in_max) / in_max; in_max None = 65535) or float32 -> float32
+    [B, ceil(H * scale), ceil(W * scale)]: the MATLAB-style antialiased bicubic down-scaling behind the low-resolution image
+    of an HR-only pair (resize.hip; utils_image.py:1358-1422,1505-1578)."""
     if not src.is_cuda:
         raise SrhipError("srhip ops need CUDA/HIP tensors (no CPU fallback exists)")
-    assert src.dim() == 3 and src.is_contiguous() and src.dtype in (torch.uint8, torch.float32), (src.shape, src.dtype)
+    assert src.dim() == 3 and src.is_contiguous() and src.dtype in (torch.uint8, torch.uint16, torch.float32), \
+        (src.shape, src.dtype)
     import math
     B, H, W = src.shape
     scale = float(scale)
@@ -1864,7 +1897,10 @@ def imresize_aa(src, scale, out=None):
         out = torch.empty(B, Ho, Wo, device=src.device, dtype=torch.float32)
     assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, Ho, Wo), out.shape
     tmp = SCRATCH.get("imresize_aa_rows", B * Ho * W, torch.float32, src.device)
-    call("srhip_imresize_aa", _p(src), int(src.dtype == torch.uint8), _p(tmp), _p(out), B, H, W, Ho, Wo, scale, _st())
+    if src.dtype == torch.uint16:
+        call("srhip_imresize_aa_u16", _p(src), _in_max(in_max, "imresize_aa"), _p(tmp), _p(out), B, H, W, Ho, Wo, scale, _st())
+    else:
+        call("srhip_imresize_aa", _p(src), int(src.dtype == torch.uint8), _p(tmp), _p(out), B, H, W, Ho, Wo, scale, _st())
     return out
 
 
@@ -2037,25 +2073,32 @@ def origin_sample(table, ids, uniforms):
     return out
 
 
-def train_batch(hr_tiles, lr_tiles, ids, y0, x0, modes, patch_size, sf):
+def train_batch(hr_tiles, lr_tiles, ids, y0, x0, modes, patch_size, sf, in_max=None):
     """The batch dict the reference's trainer feeds ModelPlain (keys l_im, h_im; dataset_dpsr.py:981-1005)
     from resident tiles: HR crop at (y0, x0), LR crop at (y0 // sf, x0 // sf) of size patch_size // sf,
-    the same augmentation mode on both (dataset_dpsr.py:866-894).  An LR tile is uint8 (a true or CACO-2-synthesised
-    tile) or float32 (the antialiased down-scaling of an HR-only pair, imresize_aa); one batch may hold both."""
+    the same augmentation mode on both (dataset_dpsr.py:866-894).  An HR tile is uint8 or uint16; an LR tile is uint8 (a true
+    or CACO-2-synthesised tile), uint16 (a true 16-bit tile) or float32 (the antialiased down-scaling of an HR-only pair,
+    imresize_aa).  uint16 tiles are read at full depth with the white level ``in_max`` (patch_gather_u16).  One batch may mix
+    them, and so may one pair: each gather fills its own samples."""
     ly, lx, lp = [v // sf for v in y0], [v // sf for v in x0], patch_size // sf
-    B = len(ids)
-    f32 = [lr_tiles[i].dtype == torch.float32 for i in ids]
-    if not any(f32):
-        l_im = patch_gather(lr_tiles, ids, ly, lx, modes, lp)
-    elif all(f32):
-        l_im = patch_gather_f32(lr_tiles, ids, ly, lx, modes, lp)
-    else:                         # a mixed batch: each gather fills its own samples
-        l_im = torch.empty(B, 1, lp, lp, device=lr_tiles[ids[0]].device, dtype=torch.float32)
-        for want, gather in ((False, patch_gather), (True, patch_gather_f32)):
-            sel = [b for b in range(B) if f32[b] == want]
+    gathers = {torch.uint8: patch_gather, torch.float32: patch_gather_f32,
+               torch.uint16: lambda *a: patch_gather_u16(*a, in_max=in_max)}
+
+    def gather(what, ok, tiles, yy, xx, P):
+        kinds = [tiles[i].dtype for i in ids]
+        if any(k not in ok for k in kinds):
+            raise ValueError(f"train_batch: {what} tiles must be {' / '.join(str(k)[6:] for k in ok)} (got {set(kinds) - set(ok)})")
+        if len(set(kinds)) == 1:
+            return gathers[kinds[0]](tiles, ids, yy, xx, modes, P)
+        out = torch.empty(len(ids), 1, P, P, device=tiles[ids[0]].device, dtype=torch.float32)
+        for kind in gathers:          # a mixed batch: each gather fills its own samples
+            sel = [b for b in range(len(ids)) if kinds[b] == kind]
             pick = lambda v: [v[b] for b in sel]
-            l_im[sel] = gather(lr_tiles, pick(ids), pick(ly), pick(lx), pick(modes), lp)
-    return {"h_im": patch_gather(hr_tiles, ids, y0, x0, modes, patch_size), "l_im": l_im}
+            if sel:
+                out[sel] = gathers[kind](tiles, pick(ids), pick(yy), pick(xx), pick(modes), P)
+        return out
+    l_im = gather("LR", (torch.uint8, torch.uint16, torch.float32), lr_tiles, ly, lx, lp)
+    return {"h_im": gather("HR", (torch.uint8, torch.uint16), hr_tiles, y0, x0, patch_size), "l_im": l_im}
 
 
 # ------------------------------------------------------------------ metrics

@@ -7,8 +7,10 @@ and ``best-models/G-model.pth``.  Per group of at most ``batch`` pages the devic
 ``ModelPlain.test`` or one of the test modes --, one ``srhip_emit_uint`` (crop, clamp, scale, round, cast, non-finite flag)
 and one download.
 
-The 16-bit path feeds a net that was trained on 8-bit data with finer grey levels (v / 65535, or v / in_max for e.g. 12-bit
-data in a 16-bit container): the reference has no such path, so nothing pins its quality.
+16-bit pages are read as v / 65535, or v / in_max for e.g. 12-bit data in a 16-bit container: the rule by which main.py reads
+16-bit tiles, so a net trained on such a fold sees here what it saw in training; without ``in_max`` the white level that
+run recorded in ``config_model.yml`` (--in_max) applies.  A net trained on 8-bit data gets finer grey levels than it has seen:
+the reference has no such path, so nothing pins the quality of that combination.
 
 What cannot be done is refused by name before anything runs on the device (``PredictError``): 16-bit pages with SRCNN (its
 input is cv2's fixed-point cubic interpolation of a uint8 image) or DSR-Splines (one spline net per grey level 0 .. 255),
@@ -74,6 +76,8 @@ def check_request(args, dtype, H, W, in_max=None, out_dtype="same"):
                            "uint8 image")
     if name == "uint16" and net == constants.DSRSPLINES:
         raise PredictError("DSR-Splines takes 8-bit pages only: it holds one spline net per grey level 0 .. 255")
+    if in_max is None and name == "uint16":         # the white level the folder's run trained with (main.py --in_max), if any
+        in_max = getattr(args, "in_max", None)
     if in_max is None:
         in_max = _RANGE[name]
     if int(in_max) != in_max or not 1 <= in_max <= _RANGE[name]:
