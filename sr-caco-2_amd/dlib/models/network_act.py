@@ -11,7 +11,7 @@ import math
 import torch
 import torch.nn as nn
 
-from dlib.models.network_dbpn import TapeNet
+from dlib.models.engine_net import TapeNet
 
 __all__ = ['ACT']
 

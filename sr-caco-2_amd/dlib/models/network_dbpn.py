@@ -6,7 +6,7 @@ libsrhip kernels).  1-channel inputs; GPU only (CPU tensors raise)."""
 import torch
 import torch.nn as nn
 
-from srhip.module_path import refresh_if_params_changed
+from dlib.models.engine_net import TapeNet
 
 __all__ = ['DBPN']
 
@@ -61,77 +61,6 @@ class DownBlock(nn.Module):                                       # network_dbpn
         self.down_conv1 = ConvBlock(nf, nf, k, s, p)
         self.down_conv2 = DeconvBlock(nf, nf, k, s, p)
         self.down_conv3 = ConvBlock(nf, nf, k, s, p)
-
-
-class _NetFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, net, need_grad, *params):
-        ctx.net = net
-        from srhip import ops
-        with ops.amp_inference(getattr(net, "amp", False) and not need_grad):       # --amp: inference only
-            y = net.engine.forward(x, None, save=need_grad)
-        return y.clone() if need_grad else y
-
-    @staticmethod
-    def backward(ctx, dy):
-        net = ctx.net
-        names = [k for k, _ in net.named_parameters()]
-        grads = {k: torch.empty_like(p) for k, p in net.named_parameters()}
-        net.engine.backward(dy.contiguous(), grads)
-        return (None, None, None) + tuple(grads[k] for k in names)
-
-
-class TapeNet(nn.Module):
-    """What every tape-engine mirror shares: lazy engine, invalidation hooks, the TrainStep protocol."""
-    engine_cls = None
-
-    def _init_protocol(self, upscale, in_chans):
-        if in_chans != 1:
-            raise NotImplementedError(f"{type(self).__name__} on libsrhip: 1-channel microscopy patches only")
-        self.upscale, self.scale, self.in_chans = upscale, upscale, in_chans
-        self._engine = None
-
-    @property
-    def engine(self):
-        if self._engine is None:
-            self._engine = self._make_engine()
-        return self._engine
-
-    def _apply(self, fn, *a, **k):
-        out = super()._apply(fn, *a, **k)
-        self._engine = None
-        return out
-
-    def load_state_dict(self, *a, **k):
-        out = super().load_state_dict(*a, **k)
-        if self._engine is not None:
-            self._engine.invalidate()
-        return out
-
-    def weights_changed(self):
-        if self._engine is not None:
-            self._engine.invalidate()
-
-    def sample_drop_path(self, batch, device):
-        return None
-
-    def flush(self):
-        pass
-
-    def prepare_input(self, x):
-        if not x.is_cuda:
-            raise RuntimeError(f"{type(self).__name__} (libsrhip) runs on the GPU only: move the model and the input to "
-                               f"cuda; there is no CPU fallback")
-        assert x.dim() == 4 and x.shape[1] == self.in_chans, f'c: {x.shape}, img-nc: {self.in_chans}'
-        return x.float().contiguous()[:, 0], x.shape[2], x.shape[3]
-
-    def forward(self, x):
-        self.flush()
-        xi, h, w = self.prepare_input(x)
-        params = [p for _, p in self.named_parameters()]
-        need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-        refresh_if_params_changed(self, params)   # stock torch.optim wrote the weights?
-        return _NetFn.apply(xi, self, need_grad, *params)
 
 
 class DBPN(TapeNet):

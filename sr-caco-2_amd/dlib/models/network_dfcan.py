@@ -6,7 +6,7 @@ spectrum's magnitude as a separable DFT with f64 accumulation.  Trains (srhip.ta
 LR images up to 256 x 256; GPU only."""
 import torch.nn as nn
 
-from dlib.models.network_dbpn import TapeNet
+from dlib.models.engine_net import TapeNet
 
 __all__ = ['DFCAN']
 

@@ -8,7 +8,7 @@ import torch
 import torch.nn as nn
 
 from dlib.utils import constants
-from srhip.module_path import refresh_if_params_changed
+from dlib.models.engine_net import EngineNet
 
 __all__ = ['DsrSplines']
 
@@ -35,28 +35,9 @@ class _SplineNet(nn.Module):
                                      for i in range(len(widths) - 1)])
 
 
-class _NetFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, net, need_grad, *params):
-        ctx.net = net
-        y = net.engine.forward(x, None, save=need_grad)      # --amp evaluation runs the same float32 kernels
-        return y.clone() if need_grad else y
+class DsrSplines(EngineNet):
+    display_name = "DSR-Splines"
 
-    @staticmethod
-    def backward(ctx, dy):
-        net = ctx.net
-        eng = net.engine
-        # the gradients as views of one buffer in the kernels' table layout: written in place by one launch
-        flat = torch.empty(eng.n * eng.P, device=dy.device)
-        grads, off = {}, 0
-        for k, p in net.named_parameters():
-            grads[k] = flat[off:off + p.numel()].view_as(p)
-            off += (p.numel() + 3) // 4 * 4
-        eng.backward(dy.contiguous(), grads)
-        return (None, None, None) + tuple(grads[k] for k in eng.names)
-
-
-class DsrSplines(nn.Module):
     def __init__(self, upscale: int, in_planes: int, in_ksz: int, splinenet_type: str, n_splines_per_color: int,
                  use_global_residual: bool, use_local_residual: bool, color_min: int = 0, color_max: int = 255) -> None:
         super().__init__()
@@ -87,49 +68,26 @@ class DsrSplines(nn.Module):
         self.n_splines = len(self.knots)
         self.global_residual = None
         self.x_interp = None
-        self._engine = None
 
     def flush(self):
         """The reference's save path calls it (it drops the masks and predictions kept by the forward): nothing is kept here."""
         self.global_residual = None
         self.x_interp = None
 
-    @property
-    def engine(self):
-        if self._engine is None:
-            from srhip.dsr_splines_engine import DsrSplinesEngine
-            self._engine = DsrSplinesEngine(self)
-        return self._engine
+    def _make_engine(self):
+        from srhip.dsr_splines_engine import DsrSplinesEngine
+        return DsrSplinesEngine(self)
 
-    def _apply(self, fn, *a, **k):
-        out = super()._apply(fn, *a, **k)
-        self._engine = None
-        return out
+    def engine_forward(self, xi, dp, need_grad):
+        return self.engine.forward(xi, dp, save=need_grad)      # --amp evaluation runs the same float32 kernels
 
-    def load_state_dict(self, *a, **k):
-        out = super().load_state_dict(*a, **k)
-        if self._engine is not None:
-            self._engine.invalidate()
-        return out
-
-    def weights_changed(self):
-        if self._engine is not None:
-            self._engine.invalidate()
-
-    def sample_drop_path(self, batch, device):
-        return None
-
-    def prepare_input(self, x):
-        if not x.is_cuda:
-            raise RuntimeError("DSR-Splines (libsrhip) runs on the GPU only: move the model and the input to cuda; "
-                               "there is no CPU fallback")
-        assert x.dim() == 4 and x.shape[1] == self.in_planes, f'c: {x.shape}, img-nc: {self.in_planes}'
-        return x.float().contiguous()[:, 0], x.shape[2], x.shape[3]
-
-    def forward(self, x):
-        self.flush()
-        xi, h, w = self.prepare_input(x)
-        params = [p for _, p in self.named_parameters()]
-        need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-        refresh_if_params_changed(self, params)   # stock torch.optim wrote the weights?
-        return _NetFn.apply(xi, self, need_grad, *params)
+    def grad_buffers(self):
+        """The gradients as views of one buffer in the kernels' table layout (each tensor padded to four floats): written in
+        place by one launch."""
+        named = list(self.named_parameters())
+        flat = torch.empty(sum((p.numel() + 3) // 4 * 4 for _, p in named), device=named[0][1].device)
+        grads, off = {}, 0
+        for k, p in named:
+            grads[k] = flat[off:off + p.numel()].view_as(p)
+            off += (p.numel() + 3) // 4 * 4
+        return grads

@@ -16,8 +16,7 @@ import math
 import torch
 import torch.nn as nn
 
-from srhip import ops
-from srhip.module_path import refresh_if_params_changed
+from dlib.models.engine_net import EngineNet
 
 __all__ = ['EDSR_LIIF', 'EDSR']
 
@@ -34,26 +33,10 @@ def _conv3(co, ci):
     return m
 
 
-class _NetFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, net, need_grad, *params):
-        ctx.net = net
-        ctx.need_dx = x.requires_grad
-        # reduced-precision matmuls only for inference (net.amp, set by --amp): training stays f32-accurate
-        with ops.amp_inference(getattr(net, "amp", False) and not need_grad):
-            y = net.engine.forward(x, None, save=need_grad)
-        return y.clone() if need_grad else y
+class EDSR_LIIF(EngineNet):
+    display_name = "EDSR"
+    input_grad = True           # the engine hands back dx
 
-    @staticmethod
-    def backward(ctx, dy):
-        net = ctx.net
-        names = [k for k, _ in net.named_parameters()]
-        grads = {k: torch.empty_like(p) for k, p in net.named_parameters()}
-        dx = net.engine.backward(dy.contiguous(), grads, need_dx=ctx.need_dx)
-        return (dx, None, None) + tuple(grads[k] for k in names)
-
-
-class EDSR_LIIF(nn.Module):
     def __init__(self, in_chans=1, n_resblocks=16, n_feats=64, scale=2, rgb_range=1.,
                  local_ensemble=True, feat_unfold=True, cell_decode=True, res_scale=1., **kwargs):
         super().__init__()
@@ -77,46 +60,10 @@ class EDSR_LIIF(nn.Module):
         for _ in range(int(math.log2(scale))):
             up += [_conv3(4 * n_feats, n_feats), nn.Identity()]
         self.tail = nn.ModuleList([nn.ModuleList(up), _conv3(in_chans, n_feats)])
-        self._engine = None
 
-    @property
-    def engine(self):
-        if self._engine is None:
-            from srhip.edsr_engine import EDSREngine
-            self._engine = EDSREngine(self)
-        return self._engine
-
-    def _apply(self, fn, *a, **k):
-        out = super()._apply(fn, *a, **k)
-        self._engine = None
-        return out
-
-    def load_state_dict(self, *a, **k):
-        out = super().load_state_dict(*a, **k)
-        if self._engine is not None:
-            self._engine.invalidate()
-        return out
-
-    def weights_changed(self):
-        if self._engine is not None:
-            self._engine.invalidate()
-
-    def sample_drop_path(self, batch, device):
-        return None
-
-    def prepare_input(self, x):
-        if not x.is_cuda:
-            raise RuntimeError("EDSR (libsrhip) runs on the GPU only: move the model and the input "
-                               "to cuda; there is no CPU fallback")
-        assert x.dim() == 4 and x.shape[1] == 1, x.shape
-        return x.float().contiguous()[:, 0], x.shape[2], x.shape[3]
-
-    def forward(self, x):
-        xi, h, w = self.prepare_input(x)
-        params = [p for _, p in self.named_parameters()]
-        need_grad = torch.is_grad_enabled() and (xi.requires_grad or any(p.requires_grad for p in params))
-        refresh_if_params_changed(self, params)   # stock torch.optim wrote the weights?
-        return _NetFn.apply(xi, self, need_grad, *params)
+    def _make_engine(self):
+        from srhip.edsr_engine import EDSREngine
+        return EDSREngine(self)
 
 
 EDSR = EDSR_LIIF

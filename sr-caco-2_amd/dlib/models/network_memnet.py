@@ -8,7 +8,7 @@ statistics in eval mode).  1-channel inputs; GPU only (CPU tensors raise)."""
 import torch
 import torch.nn as nn
 
-from srhip.module_path import refresh_if_params_changed
+from dlib.models.engine_net import EngineNet
 
 __all__ = ['MemNet']
 
@@ -31,28 +31,7 @@ class _MemoryBlock(nn.Module):                     # network_memnet.py:44-78
                                        nn.Conv2d(gate_channels, channels, (1, 1), (1, 1), (0, 0), bias=False))
 
 
-class _NetFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, net, need_grad, *params):
-        ctx.net = net
-        # --amp (inference only; training stays f32-accurate): the convs run ONE product of the operands' leading fp16 planes
-        # (11 significant bits under the block exponents) -- PSNR within 0.003 dB of the f32-accurate forward on the
-        # seeded-weights check (gate 0.01 dB, tests/test_gpu_amp.py; with one bf16 product, round 2, VDSR was 0.023 dB off)
-        from srhip import ops
-        with ops.amp_inference(getattr(net, "amp", False) and not need_grad):
-            y = net.engine.forward(x, None, save=need_grad)
-        return y.clone() if need_grad else y
-
-    @staticmethod
-    def backward(ctx, dy):
-        net = ctx.net
-        names = [k for k, _ in net.named_parameters()]
-        grads = {k: torch.empty_like(p) for k, p in net.named_parameters()}
-        net.engine.backward(dy.contiguous(), grads)
-        return (None, None, None) + tuple(grads[k] for k in names)
-
-
-class MemNet(nn.Module):
+class MemNet(EngineNet):
     def __init__(self, in_chans: int, upscale: int, num_memory_blocks: int, num_residual_blocks: int):
         super().__init__()
         assert isinstance(upscale, int) and upscale > 0, upscale
@@ -68,7 +47,6 @@ class MemNet(nn.Module):
                                                    for i in range(num_memory_blocks)])
         self.reconstructor = nn.Sequential(nn.BatchNorm2d(64), nn.ReLU(True),
                                            nn.Conv2d(64, in_chans, (1, 1), (1, 1), (0, 0), bias=False))
-        self._engine = None
         self._initialize_weights()
 
     def _initialize_weights(self) -> None:          # network_memnet.py:172-179
@@ -82,45 +60,15 @@ class MemNet(nn.Module):
         self.global_residual = None
         self.x_interp = None
 
-    @property
-    def engine(self):
-        if self._engine is None:
-            from srhip.memnet_engine import MemNetEngine
-            self._engine = MemNetEngine(self)
-        return self._engine
+    def _make_engine(self):
+        from srhip.memnet_engine import MemNetEngine
+        return MemNetEngine(self)
 
-    def _apply(self, fn, *a, **k):
-        out = super()._apply(fn, *a, **k)
-        self._engine = None
-        return out
-
-    def load_state_dict(self, *a, **k):
-        out = super().load_state_dict(*a, **k)
-        if self._engine is not None:
-            self._engine.invalidate()
-        return out
-
-    def weights_changed(self):
-        if self._engine is not None:
-            self._engine.invalidate()
-
-    def sample_drop_path(self, batch, device):
-        return None
-
-    def prepare_input(self, x):
-        if not x.is_cuda:
-            raise RuntimeError("MemNet (libsrhip) runs on the GPU only: move the model and the input to cuda; "
-                               "there is no CPU fallback")
-        assert x.dim() == 4 and x.shape[1] == self.in_chans, f'c: {x.shape}, img-nc: {self.in_chans}'
-        return x.float().contiguous()[:, 0], x.shape[2], x.shape[3]
-
-    def forward(self, x):
-        self.flush()
-        xi, h, w = self.prepare_input(x)
-        params = [p for _, p in self.named_parameters()]
+    def need_grad(self, xi, params):
         # gradients exist in train mode (batch statistics); eval mode is inference
-        need_grad = self.training and torch.is_grad_enabled() and any(p.requires_grad for p in params)
-        refresh_if_params_changed(self, params)   # stock torch.optim wrote the weights?
+        return self.training and super().need_grad(xi, params)
+
+    def run(self, xi, dp=None):
         if not self.training:
             # the running statistics are buffers: re-read them (80 tiny copies + one preparation launch) when something wrote
             # them since the last evaluation forward -- a training forward of the engine (it drops the flag itself: its
@@ -135,5 +83,5 @@ class MemNet(nn.Module):
             # the widest gate concatenation of the batch must stay below 2^31 elements (32-bit staging offsets of the conv /
             # GEMM kernels); past that the batch is walked per image.  (6.4 GB at B = 8, 512 x 512: nothing on this part)
             if xi.shape[0] > 1 and xi.shape[0] * per >= (1 << 31):
-                return torch.cat([_NetFn.apply(xi[b:b + 1], self, False, *params) for b in range(xi.shape[0])], 0)
-        return _NetFn.apply(xi, self, need_grad, *params)
+                return torch.cat([super(MemNet, self).run(xi[b:b + 1]) for b in range(xi.shape[0])], 0)
+        return super().run(xi)

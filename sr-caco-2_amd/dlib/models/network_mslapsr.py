@@ -10,7 +10,7 @@ import math
 import torch
 import torch.nn as nn
 
-from srhip.module_path import refresh_if_params_changed
+from dlib.models.engine_net import EngineNet
 
 __all__ = ['MSLapSRN']
 
@@ -45,30 +45,7 @@ class ConvLayer(nn.Module):        # network_mslapsr.py:53-64
         self.cl = nn.ModuleList([_Conv(channels, channels)])
 
 
-class _NetFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, net, need_grad, *params):
-        ctx.net = net
-        # --amp (inference only; training stays f32-accurate): the convs run ONE product of the operands' leading fp16 planes
-        # (11 significant bits under the block exponents) -- PSNR within 0.003 dB of the f32-accurate forward on the
-        # seeded-weights check (gate 0.01 dB, tests/test_gpu_amp.py; with one bf16 product, round 2, VDSR was 0.023 dB off)
-        from srhip import ops
-        with ops.amp_inference(getattr(net, "amp", False) and not need_grad):
-            y = net.engine.forward(x, None, save=need_grad)
-        inter = [t.clone() for t in net.engine.intermediate_outs]
-        ctx.n_inter = len(inter)
-        return (y.clone() if need_grad else y, *inter)
-
-    @staticmethod
-    def backward(ctx, dy, *d_inter):
-        net = ctx.net
-        names = [k for k, _ in net.named_parameters()]
-        grads = {k: torch.empty_like(p) for k, p in net.named_parameters()}
-        net.engine.backward(dy.contiguous(), grads, d_inter=[None if g is None else g.contiguous() for g in d_inter])
-        return (None, None, None) + tuple(grads[k] for k in names)
-
-
-class MSLapSRN(nn.Module):
+class MSLapSRN(EngineNet):
     def __init__(self, upscale: int = 2, in_chans: int = 3) -> None:
         super().__init__()
         assert upscale in [2, 4, 8], upscale
@@ -82,7 +59,6 @@ class MSLapSRN(nn.Module):
             setattr(self, f"laplacian_pyramid_conv{3 * o + 2}", _ConvT(1, 1))
             setattr(self, f"laplacian_pyramid_conv{3 * o + 3}", _Conv(in_chans, 64))
         self.intermediate_outs = []     # hold only intermediate predictions
-        self._engine = None
 
     def flush(self):
         self.intermediate_outs = []
@@ -101,44 +77,14 @@ class MSLapSRN(nn.Module):
                 m.bias.data.zero_()
         self.weights_changed()
 
-    @property
-    def engine(self):
-        if self._engine is None:
-            from srhip.mslapsrn_engine import MSLapSRNEngine
-            self._engine = MSLapSRNEngine(self)
-        return self._engine
+    def _make_engine(self):
+        from srhip.mslapsrn_engine import MSLapSRNEngine
+        return MSLapSRNEngine(self)
 
-    def _apply(self, fn, *a, **k):
-        out = super()._apply(fn, *a, **k)
-        self._engine = None
-        return out
+    def extra_outputs(self):
+        return [t.clone() for t in self.engine.intermediate_outs]
 
-    def load_state_dict(self, *a, **k):
-        out = super().load_state_dict(*a, **k)
-        if self._engine is not None:
-            self._engine.invalidate()
-        return out
-
-    def weights_changed(self):
-        if self._engine is not None:
-            self._engine.invalidate()
-
-    def sample_drop_path(self, batch, device):
-        return None
-
-    def prepare_input(self, x):
-        if not x.is_cuda:
-            raise RuntimeError("MSLapSRN (libsrhip) runs on the GPU only: move the model and the input to cuda; "
-                               "there is no CPU fallback")
-        assert x.dim() == 4 and x.shape[1] == self.in_chans, f'c: {x.shape}, img-nc: {self.in_chans}'
-        return x.float().contiguous()[:, 0], x.shape[2], x.shape[3]
-
-    def forward(self, x):
-        self.intermediate_outs = []
-        xi, h, w = self.prepare_input(x)
-        params = [p for _, p in self.named_parameters()]
-        need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-        refresh_if_params_changed(self, params)   # stock torch.optim wrote the weights?
-        y, *inter = _NetFn.apply(xi, self, need_grad, *params)
-        self.intermediate_outs = list(inter)
+    def run(self, xi, dp=None):
+        y, *inter = super().run(xi, dp)
+        self.intermediate_outs = inter
         return y

@@ -6,7 +6,7 @@ The compute is ``srhip.omnisr_engine.OmniSREngine``.  Training through the tape 
 import torch
 import torch.nn as nn
 
-from dlib.models.network_dbpn import TapeNet
+from dlib.models.engine_net import TapeNet
 
 __all__ = ['OmniSR']
 

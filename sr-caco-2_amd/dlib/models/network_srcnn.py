@@ -10,7 +10,7 @@ import math
 import torch
 import torch.nn as nn
 
-from srhip.module_path import refresh_if_params_changed
+from dlib.models.engine_net import EngineNet
 
 __all__ = ['SRCNN']
 
@@ -22,26 +22,7 @@ class _Conv(nn.Module):
         self.bias = nn.Parameter(torch.zeros(co))
 
 
-class _NetFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, net, need_grad, *params):
-        ctx.net = net
-        # --amp (inference only; training stays f32-accurate): fp16 storage of the 1024-channel feature map, one product
-        from srhip import ops
-        with ops.amp_inference(getattr(net, "amp", False) and not need_grad):
-            y = net.engine.forward(x, None, save=need_grad)
-        return y.clone() if need_grad else y
-
-    @staticmethod
-    def backward(ctx, dy):
-        net = ctx.net
-        names = [k for k, _ in net.named_parameters()]
-        grads = {k: torch.empty_like(p) for k, p in net.named_parameters()}
-        net.engine.backward(dy.contiguous(), grads)
-        return (None, None, None) + tuple(grads[k] for k in names)
-
-
-class SRCNN(nn.Module):
+class SRCNN(EngineNet):
     def __init__(self, in_chans: int) -> None:
         super().__init__()
         assert isinstance(in_chans, int) and in_chans > 0, in_chans
@@ -51,7 +32,6 @@ class SRCNN(nn.Module):
         self.features = nn.ModuleList([_Conv(1024, in_chans, 5)])        # + ReLU
         self.map = nn.ModuleList([_Conv(128, 1024, 1)])                  # + ReLU
         self.reconstruction = _Conv(in_chans, 128, 1)
-        self._engine = None
         self._initialize_weights()
 
     def _initialize_weights(self):                                       # network_srcnn.py:63-72
@@ -62,41 +42,6 @@ class SRCNN(nn.Module):
         nn.init.normal_(self.reconstruction.weight.data, 0.0, 0.001)
         nn.init.zeros_(self.reconstruction.bias.data)
 
-    @property
-    def engine(self):
-        if self._engine is None:
-            from srhip.srcnn_engine import SRCNNEngine
-            self._engine = SRCNNEngine(self)
-        return self._engine
-
-    def _apply(self, fn, *a, **k):
-        out = super()._apply(fn, *a, **k)
-        self._engine = None
-        return out
-
-    def load_state_dict(self, *a, **k):
-        out = super().load_state_dict(*a, **k)
-        if self._engine is not None:
-            self._engine.invalidate()
-        return out
-
-    def weights_changed(self):
-        if self._engine is not None:
-            self._engine.invalidate()
-
-    def sample_drop_path(self, batch, device):
-        return None
-
-    def prepare_input(self, x):
-        if not x.is_cuda:
-            raise RuntimeError("SRCNN (libsrhip) runs on the GPU only: move the model and the input to cuda; "
-                               "there is no CPU fallback")
-        assert x.dim() == 4 and x.shape[1] == self.in_chans, f'c: {x.shape}, img-nc: {self.in_chans}'
-        return x.float().contiguous()[:, 0], x.shape[2], x.shape[3]
-
-    def forward(self, x):
-        xi, h, w = self.prepare_input(x)
-        params = [p for _, p in self.named_parameters()]
-        need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-        refresh_if_params_changed(self, params)   # stock torch.optim wrote the weights?
-        return _NetFn.apply(xi, self, need_grad, *params)
+    def _make_engine(self):
+        from srhip.srcnn_engine import SRCNNEngine
+        return SRCNNEngine(self)

@@ -6,7 +6,7 @@ convs included) and PReLU(init 0.2); the compute is ``srhip.srfbn_engine.SRFBNEn
 import torch
 import torch.nn as nn
 
-from dlib.models.network_dbpn import TapeNet
+from dlib.models.engine_net import TapeNet
 
 __all__ = ['SRFBN']
 

@@ -19,10 +19,9 @@ import math
 import torch
 import torch.nn as nn
 
-from srhip import ops
-from srhip.module_path import refresh_if_params_changed
 import torch.nn.functional as F
 
+from dlib.models.engine_net import EngineNet
 from dlib.utils import constants
 
 __all__ = ['SwinIR']
@@ -125,29 +124,8 @@ class _SwinBlock(_Box):
         self.mlp = mlp
 
 
-class _NetFn(torch.autograd.Function):
-    """One autograd node for the whole network (autograd-compatible path;
-    the training loop in ModelPlain drives the engine directly)."""
-
-    @staticmethod
-    def forward(ctx, x, net, dp, need_grad, *params):
-        ctx.net = net
-        ctx.need_dx = x.requires_grad
-        # reduced-precision matmuls only for inference (net.amp, set by --amp): training stays f32-accurate
-        with ops.amp_inference(getattr(net, "amp", False) and not need_grad):
-            y = net.engine.forward(x, dp, save=need_grad)
-        return y.clone() if need_grad else y
-
-    @staticmethod
-    def backward(ctx, dy):
-        net = ctx.net
-        names = [k for k, _ in net.named_parameters()]
-        grads = {k: torch.empty_like(p) for k, p in net.named_parameters()}
-        dx = net.engine.backward(dy.contiguous(), grads, need_dx=ctx.need_dx)
-        return (dx, None, None, None) + tuple(grads[k] for k in names)
-
-
-class SwinIR(nn.Module):
+class SwinIR(EngineNet):
+    input_grad = True           # the engines hand back dx
     # forward() multiplies the input by img_range and divides the output by it (reference :935,968): the fused training
     # step (srhip/train.py) applies the same scale around the loss only for a net that says so
     forward_divides_by_img_range = True
@@ -234,7 +212,6 @@ class SwinIR(nn.Module):
                 up += [_conv3(4 * num_feat, num_feat), nn.Identity()]     # upsample.{0,2,4}: conv; odd: PixelShuffle
             self.upsample = nn.ModuleList(up)
             self.conv_last = _conv3(in_chans, num_feat)
-        self._engine = None
 
     # -- helpers -------------------------------------------------------------
     def swin_blocks(self):
@@ -242,32 +219,12 @@ class SwinIR(nn.Module):
             for b in layer.residual_group.blocks:
                 yield b
 
-    @property
-    def engine(self):
-        if self._engine is None:
-            if self.use_tape:
-                from srhip.swinir_tape_engine import SwinIRTapeEngine
-                self._engine = SwinIRTapeEngine(self)
-            else:
-                from srhip.swinir_engine import SwinIREngine
-                self._engine = SwinIREngine(self)
-        return self._engine
-
-    def _apply(self, fn, *a, **k):   # .cuda() / .to(): parameter storage moves
-        out = super()._apply(fn, *a, **k)
-        self._engine = None
-        return out
-
-    def load_state_dict(self, *a, **k):
-        out = super().load_state_dict(*a, **k)
-        if self._engine is not None:
-            self._engine.invalidate()
-        return out
-
-    def weights_changed(self):
-        """Call after parameters were modified in place (optimizer step)."""
-        if self._engine is not None:
-            self._engine.invalidate()
+    def _make_engine(self):
+        if self.use_tape:
+            from srhip.swinir_tape_engine import SwinIRTapeEngine
+            return SwinIRTapeEngine(self)
+        from srhip.swinir_engine import SwinIREngine
+        return SwinIREngine(self)
 
     def sample_drop_path(self, batch, device):
         """timm DropPath semantics (per-sample Bernoulli(keep)/keep), one row per
@@ -301,10 +258,7 @@ class SwinIR(nn.Module):
         """check_image_size (network_swinir.py:908-913): reflect-pad to a multiple of the window; (x - mean) * img_range
         (:934-935; the mean is zero unless in_chans == 3).  in_chans 1: [B, H, W]; otherwise NHWC with the channels
         zero-padded to 4 (what the engine's conv_first takes)."""
-        if not x.is_cuda:
-            raise RuntimeError("SwinIR (libsrhip) runs on the GPU only: move the model and the "
-                               "input to cuda; there is no CPU fallback")
-        assert x.dim() == 4 and x.shape[1] == self.in_chans, x.shape
+        self.check_input(x)
         _, _, h, w = x.shape
         ws = self.window_size
         ph, pw = (ws - h % ws) % ws, (ws - w % ws) % ws
@@ -326,10 +280,7 @@ class SwinIR(nn.Module):
             raise NotImplementedError("inputs must be larger than one window")
         if self.ape and tuple(xi.shape[1:3]) != self.img_size:   # the reference's broadcast fails the same way (:919)
             raise RuntimeError(f"ape=True: the input has to be img_size {self.img_size}, got {tuple(xi.shape[1:3])}")
-        params = [p for _, p in self.named_parameters()]
-        need_grad = torch.is_grad_enabled() and (xi.requires_grad or any(p.requires_grad for p in params))
-        refresh_if_params_changed(self, params)   # stock torch.optim wrote the weights?
-        y = _NetFn.apply(xi, self, dp, need_grad, *params)
+        y = self.run(xi, dp)
         if self.img_range != 1.:
             y = y / self.img_range
         if self.in_chans == 3:

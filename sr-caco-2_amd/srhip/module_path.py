@@ -1,4 +1,5 @@
-"""Helpers of the nn.Module ("drop-in") path of the network mirrors.
+"""Helpers of the nn.Module ("drop-in") path of the network mirrors (dlib/models/engine_net.py: EngineNet.run calls
+refresh_if_params_changed before every forward).
 
 The engines keep DERIVED operands (LayerNorm-folded weights, bf16x3 planes, conv
 packs, bias images) that are rebuilt by prepare() only when someone says the
