@@ -51,8 +51,7 @@ class EngineNet(nn.Module):
         nothing), ``eval_graph_default`` (evaluation replays a hipGraph unless told otherwise), ``forward_divides_by_img_range``,
         ``intermediate_outs`` (the multi-scale losses), ``mean``, ``img_range``; ``engine`` / ``_engine``, ``weights_changed``,
         ``sample_drop_path``, ``prepare_input``, ``flush``;
-      from an engine: ``bucket_prefixes``, ``invalidate``, ``train_graph_default``, ``amp_train_ok``, ``forward_h16`` /
-        ``backward_h16``, ``last_eval_path``, ``bufs``, ``saved``.
+      from an engine: what the docstring of ``Engine`` states (srhip/engine.py).
 
     Hooks of NetFn (each with the one or two nets that override it): ``input_grad`` (SwinIR, EDSR: the engine returns dx),
     ``extra_outputs`` (MSLapSRN), ``grad_buffers`` and ``engine_forward`` (DSR-Splines)."""

@@ -15,28 +15,20 @@ import torch
 
 from . import ops
 from .planes import PlaneCache
-from .swinir_engine import _Bufs
-from .tape import Tape, WeightBank
+from .tape import Tape, TapeEngine
 
 
-class ACTEngine:
-    train_graph_default = True      # ModelPlain replays the training step from a hipGraph (TrainStep.step_graph)
+class ACTEngine(TapeEngine):
+    need_dx_refusal = "ACT: no gradient with respect to the input image"
 
     def __init__(self, net):
-        self.net = net
-        self.bank = WeightBank()
+        super().__init__(net)
         self.planes = PlaneCache()
-        self.bufs = _Bufs()
-        self.prepared = False
-        self.saved = None
         self.taps = None          # tests: dict that receives intermediate tensors (names as oracle.act_forward's taps)
 
     def invalidate(self):
-        self.prepared = False
+        super().invalidate()
         self.planes.clear()
-
-    def bucket_prefixes(self):
-        return [[""]]
 
     # ------------------------------------------------------------------ weights
     def _convs3(self):
@@ -52,9 +44,8 @@ class ACTEngine:
         out.append(("conv_last", net.conv_last))
         return out
 
-    def prepare(self):
+    def bank_entries(self):
         net, bank = self.net, self.bank
-        bank.begin()
         for key, m in self._convs3():
             bank.conv(key, m.weight, m.bias, "c3")
         F = net.n_feats
@@ -62,8 +53,6 @@ class ACTEngine:
             c = net.tail[0][2 * st]
             for j in range(4):
                 bank.conv(f"tail.0.{2 * st}.{j}", c.weight[j * F:(j + 1) * F], c.bias[j * F:(j + 1) * F], "c3")
-        bank.finish(next(net.parameters()).device)
-        self.prepared = True
 
     # ------------------------------------------------------------------ pieces
     def _conv3(self, key, x, out=None, relu=False):
@@ -154,8 +143,7 @@ class ACTEngine:
 
     # ------------------------------------------------------------------ forward
     def forward(self, x3, dp=None, save=False):
-        if not self.prepared:
-            self.prepare()
+        self.ensure_prepared()
         net = self.net
         if net.dropout_rate > 0.0 and net.training:
             if dp is None:          # the autograd path (TrainStep draws the seed itself)
@@ -384,10 +372,3 @@ class ACTEngine:
             self.saved = (t, out)
         Bo, Ho, Wo = out.t.shape
         return out.t.view(Bo, 1, Ho, Wo)
-
-    def backward(self, dy, grads, need_dx=False, on_layer_done=None, grads_zeroed=False):
-        assert self.saved is not None, "backward() without a saved forward"
-        assert not need_dx, "ACT: no gradient with respect to the input image"
-        tape, out = self.saved
-        tape.backward(out, dy.reshape(out.t.shape).contiguous(), grads)
-        return None

@@ -17,26 +17,20 @@ shared convs are summed over the U applications.
 import torch
 
 from . import ops
-from .swinir_engine import _Bufs, bicubic_clamped
+from .engine import Engine
 
 CH = 128
 
 
-class DRRNEngine:
+class DRRNEngine(Engine):
+    need_dx_refusal = "DRRN (libsrhip): no gradient through the bicubic interpolation of the input"
+
     def __init__(self, net):
-        self.net = net
+        super().__init__(net)
         self.U = net.trunk.num_residual_unit
-        self.bufs = _Bufs()
-        self.derived = _Bufs()
         self.ws = ops.WeightSet()
         self.ws.use_bx3 = ops.bx3_nt_for(CH)
-        self._prep = self._prep_sig = None
-        self.prepared = False
-        self.saved = None
         self.saved_h16 = None           # what forward_h16(save=True) kept for backward_h16
-
-    def invalidate(self):
-        self.prepared = False
 
     def bucket_prefixes(self):
         """0.30 M parameters: one gradient bucket."""
@@ -47,16 +41,12 @@ class DRRNEngine:
         return [("wa", ru[1]), ("wb", ru[3])]
 
     def prepare(self):
-        ops.prepare_conv_packs(self, ((name, conv.weight.data, False) for name, conv in self._convs()))
-
-    def interpolate(self, x):
-        return bicubic_clamped(x, self.net.upscale)
+        self.prepare_conv_packs((name, conv.weight.data, False) for name, conv in self._convs())
 
     def amp_train_ok(self):
         """Whether this configuration trains under --amp on fp16 storage (forward_h16(save=True) + backward_h16): the fp16x2
         packs of both shared convs in both directions."""
-        if not self.prepared:
-            self.prepare()
+        self.ensure_prepared()
         return self.ws.use_bx3 and all(self.ws[n + s].fmt == 1 for n, _ in self._convs() for s in (".wp", ".wpt"))
 
     def _amp_train_refusal(self):
@@ -69,8 +59,7 @@ class DRRNEngine:
         evaluation ("h." buffers, two rotating unit outputs).  save=True: the --amp training forward (autocast's fp16 maps,
         model_plain.py:322-327): x0 and every unit's a_k, r_{k+1} are kept in "a." buffers of their own -- an evaluation
         forward in between overwrites none of them."""
-        if not self.prepared:
-            self.prepare()
+        self.ensure_prepared()
         if save and not self.amp_train_ok():
             raise NotImplementedError(self._amp_train_refusal())
         net, U = self.net, self.U
@@ -97,8 +86,7 @@ class DRRNEngine:
 
     def forward(self, x, dp=None, save=True):
         """x [B,H,W] (LR) -> [B,1,s*H,s*W]."""
-        if not self.prepared:
-            self.prepare()
+        self.ensure_prepared()
         if not save and ops.h16_eval() and self.ws.use_bx3 and self.ws["wa.wp"].fmt == 1:
             self.last_eval_path = "fp16 storage"
             return self.forward_h16(x)
@@ -106,11 +94,7 @@ class DRRNEngine:
         xi = self.interpolate(x[:, None])
         B, H, W = xi.shape
         dev = x.device
-        tag = "t" if save else "e"
-
-        def buf(name, *shape):
-            return self.bufs.get(f"{tag}.{name}", *shape, device=dev)
-
+        buf = self.bufs.tagged("t." if save else "e.", dev)
         x0 = buf("x0", B, H, W, CH)
         ops.conv3x3_cin1_fwd(xi, net.conv1[1].weight.data, None, CH, out=x0, relu=True)
         r = x0
@@ -136,16 +120,10 @@ class DRRNEngine:
         return y.view(B, 1, H, W)
 
     def backward(self, dy, grads, need_dx=False, on_layer_done=None, grads_zeroed=False):
-        sv = self.saved
-        assert sv is not None, "backward() without a saved forward"
-        assert not need_dx, "DRRN (libsrhip): no gradient through the bicubic interpolation of the input"
+        sv = self.saved_for_backward(need_dx)
         net, U = self.net, self.U
         B, H, W = sv["B"], sv["H"], sv["W"]
-        dev = dy.device
-
-        def buf(name, *shape):
-            return self.bufs.get("g." + name, *shape, device=dev)
-
+        buf = self.bufs.tagged("g.", dy.device)
         dy = dy.reshape(B, H, W).contiguous()
         ops.conv3x3_cin1_wgrad(dy, sv["r_last"], grads["conv2.1.weight"], None, flip=True)
         gu, ga, gx0 = buf("gu", B, H, W, CH), buf("ga", B, H, W, CH), buf("gx0", B, H, W, CH)
@@ -188,7 +166,7 @@ class DRRNEngine:
         the fp16 per-application gradients of autocast's cached fp16 weight copy in fp16)."""
         sv = self.saved_h16
         assert sv is not None, "backward_h16() without a saved forward_h16(save=True)"
-        assert not need_dx, "DRRN (libsrhip): no gradient through the bicubic interpolation of the input"
+        assert not need_dx, self.need_dx_refusal
         net, U = self.net, self.U
         B, H, W = sv["B"], sv["H"], sv["W"]
         dev = dy.device

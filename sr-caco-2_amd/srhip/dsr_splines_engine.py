@@ -15,12 +15,14 @@ engine's own (module path) and one unpacks the gradients."""
 import torch
 
 from . import ops
-from .swinir_engine import _Bufs, bicubic_clamped
+from .engine import Engine
 
 
-class DsrSplinesEngine:
+class DsrSplinesEngine(Engine):
+    need_dx_refusal = "DSR-Splines (libsrhip): no gradient through the bicubic interpolation of the input"
+
     def __init__(self, net):
-        self.net = net
+        super().__init__(net)
         self.n = net.n_splines
         self.ksz = net.in_ksz
         self.nh = len(net.h_layers)
@@ -29,16 +31,9 @@ class DsrSplinesEngine:
         self.P = ops.dsr_splines_table_floats(self.ksz, self.nh, self.local)
         self.names = [k for k, _ in net.named_parameters()]
         self.T = len(self.names) // self.n
-        self.bufs = _Bufs()
-        self.derived = _Bufs()
         self.lut = None
         self._ptrs = {}
         self.table = self._zeroed = None
-        self.prepared = False
-        self.saved = None
-
-    def invalidate(self):
-        self.prepared = False
 
     def bucket_prefixes(self):
         """At most 3.8 M parameters, all written by one launch: one gradient bucket."""
@@ -92,18 +87,13 @@ class DsrSplinesEngine:
         self.prepared = True
 
     # ---- forward / backward
-    def interpolate(self, x):
-        """network_dsr_splines.py:376-387: [B,1,h,w] -> [B,s*h,s*w], bicubic (align_corners False), clamped."""
-        return bicubic_clamped(x, self.net.upscale)
-
     def forward(self, x, dp=None, save=True):
         """x [B,h,w] (LR) -> [B,1,s*h,s*w]."""
         return self.forward_interp(self.interpolate(x[:, None]), save=save)
 
     def forward_interp(self, xi, save=True):
         """xi [B,H,W]: the clamped interpolated image."""
-        if not self.prepared:
-            self.prepare()
+        self.ensure_prepared()
         B, H, W = xi.shape
         pad = (self.ksz - 1) // 2
         if H <= pad or W <= pad:
@@ -124,9 +114,7 @@ class DsrSplinesEngine:
         return y.view(B, 1, H, W)
 
     def backward(self, dy, grads, need_dx=False, on_layer_done=None, grads_zeroed=False):
-        sv = self.saved
-        assert sv is not None, "backward() without a saved forward"
-        assert not need_dx, "DSR-Splines (libsrhip): no gradient through the bicubic interpolation of the input"
+        sv = self.saved_for_backward(need_dx)
         xi = sv["xi"]
         gl = [grads[k] for k in self.names]
         gt = self._in_place(gl)

@@ -14,32 +14,27 @@ import os
 import torch
 
 from . import ops
-from .swinir_engine import _Bufs
+from .engine import Engine
 
 
-class EDSREngine:
-    train_graph_default = True      # ModelPlain replays the training step from a hipGraph (TrainStep.step_graph)
+class EDSREngine(Engine):
+    train_graph_default = True
 
     def __init__(self, net):
-        self.net = net
+        super().__init__(net)
         self.F = net.n_feats
         self.nb = net.n_resblocks
         self.stages = int(math.log2(net.scale))
-        self.bufs = _Bufs()
-        self.derived = _Bufs()
         self.ws = ops.WeightSet()
         # conv forward / data gradient on the bf16x3 kernels from 64 features on; the weight gradients of a
         # 64-feature net stay on the exact-f32 MFMA kernels (ops.conv3x3_wgrad decides by ops.bx3_for)
         self.ws.use_bx3 = ops.bx3_nt_for(self.F)
-        self._prep = self._prep_sig = None
-        self.prepared = False
         # weight gradients on a side stream beside the data-gradient chain (backward): SRHIP_EDSR_SIDE_WGRAD=1.  Measured
         # (round 5, EDSR x8, B = 8, same box, two rounds): 1715.2 / 1715.0 patches/s on one stream, 1687.3 / 1671.7 with the
         # side stream -- the chain's one-block-per-CU launches do not leave the weight-gradient blocks room they could use
         # (both slow down); off.
         self.side_wgrad = os.environ.get("SRHIP_EDSR_SIDE_WGRAD", "0") == "1"
         self.wstream = None
-        self.saved = None
         self.saved_h16 = None           # what forward_h16(save=True) kept for backward_h16
         # Upsampler stage = conv F -> 4F + PixelShuffle(2) as one kernel per direction (no [B,H,W,4F] tensor,
         # no shuffle launches); SRHIP_FUSE_PS=0: conv + index kernel
@@ -52,9 +47,6 @@ class EDSREngine:
         # ... where a conv launch is latency-bound: the fused kernel recomputes the first conv on a one-pixel ring around its
         # 4 x 16 tile (108 mid pixels for 64), which a launch that fills the chip many times over pays in matrix-core time
         self.fuse_rb_maxpix = int(os.environ.get("SRHIP_FUSE_RESBLOCK_MAXPIX", str(8 * 64 * 64)))
-
-    def invalidate(self):
-        self.prepared = False
 
     def bucket_prefixes(self):
         """EDSR-baseline has 1.4-1.7 M parameters (5.5-6.7 MB): one gradient bucket."""
@@ -71,8 +63,8 @@ class EDSREngine:
 
     def prepare(self):
         # planes: all conv packs by one launch, the upsampler's in the order of its fused PixelShuffle
-        ops.prepare_conv_packs(self, ((name, conv.weight.data, self.fuse_ps and name.startswith("up"))
-                                      for name, conv in self._body_convs()))
+        self.prepare_conv_packs((name, conv.weight.data, self.fuse_ps and name.startswith("up"))
+                                for name, conv in self._body_convs())
 
     # ------------------------------------------------------------------ forward
     def _h16_ok(self):
@@ -82,8 +74,7 @@ class EDSREngine:
     def amp_train_ok(self):
         """Whether this configuration trains under --amp on fp16 storage (forward_h16(save=True) + backward_h16): the fp16x2
         packs of every conv in both directions, 64 .. 256 features, a power of two (the 1-channel ends' weight gradient)."""
-        if not self.prepared:
-            self.prepare()
+        self.ensure_prepared()
         return (self._h16_ok() and self.F in (64, 128, 256)
                 and all(self.ws[n + ".wpt"].fmt == 1 for n, _ in self._body_convs()))
 
@@ -103,10 +94,7 @@ class EDSREngine:
         dev = x.device
         if save and not self.amp_train_ok():
             raise NotImplementedError(self._amp_train_refusal())
-        tag = "a." if save else "h."
-
-        def buf(name, *shape):
-            return self.bufs.get(tag + name, *shape, device=dev, dtype=torch.float16)
+        buf = self.bufs.tagged("a." if save else "h.", dev, torch.float16)
         f0 = ops.conv3x3_cin1_h16(x, net.head[0].weight.data, net.head[0].bias.data, F, out=buf("f0", B, H, W, F))
         r, rs = f0, float(net.res_scale)
         blocks = []
@@ -134,19 +122,14 @@ class EDSREngine:
 
     def forward(self, x, dp=None, save=True):
         """x [B,H,W] -> [B,1,s*H,s*W]."""
-        if not self.prepared:
-            self.prepare()
+        self.ensure_prepared()
         if not save and ops.h16_eval() and self._h16_ok():
             self.last_eval_path = "fp16 storage"
             return self.forward_h16(x)
         net, F, D = self.net, self.F, self.derived
         B, H, W = x.shape
         dev = x.device
-        tag = "t" if save else "e"
-
-        def buf(name, *shape):
-            return self.bufs.get(f"{tag}.{name}", *shape, device=dev)
-
+        buf = self.bufs.tagged("t." if save else "e.", dev)
         f0 = buf("f0", B, H, W, F)
         ops.conv3x3_cin1_fwd(x, net.head[0].weight.data, net.head[0].bias.data, F, out=f0)
         r = f0
@@ -191,15 +174,12 @@ class EDSREngine:
 
     # ------------------------------------------------------------------ backward
     def backward(self, dy, grads, need_dx=False, on_layer_done=None, grads_zeroed=False):
-        sv = self.saved
-        assert sv is not None, "backward() without a saved forward"
+        sv = self.saved_for_backward()
         net, F, D = self.net, self.F, self.derived
         B, H, W = sv["B"], sv["H"], sv["W"]
         dev = dy.device
         rs = float(net.res_scale)
-
-        def buf(name, *shape):
-            return self.bufs.get("g." + name, *shape, device=dev)
+        buf = self.bufs.tagged("g.", dev)
 
         def G(name):
             return grads[name]
@@ -336,9 +316,7 @@ class EDSREngine:
         B, H, W = sv["B"], sv["H"], sv["W"]
         dev = dy.device
         rs = float(net.res_scale)
-
-        def buf(name, *shape):
-            return self.bufs.get("ag." + name, *shape, device=dev, dtype=torch.float16)
+        buf = self.bufs.tagged("ag.", dev, torch.float16)
 
         def G(name):
             return grads[name]

@@ -13,36 +13,37 @@ import torch.nn.functional as F
 
 from . import ops
 from .planes import PlaneCache
-from .swinir_engine import _Bufs
-from .tape import Tape, WeightBank
+from .tape import Tape, TapeEngine
 
 
 def _pad4(n):
     return (n + 3) // 4 * 4
 
 
-class GRLEngine:
-    train_graph_default = True      # ModelPlain replays the training step from a hipGraph (TrainStep.step_graph)
+class GRLEngine(TapeEngine):
+    """``prepared``: the tape graph's bank; the evaluation forward prepares nothing (its weights: ``_w``, ``planes``)."""
+    need_dx_refusal = "GRL: no gradient with respect to the input image"
 
     def __init__(self, net):
-        self.net = net
-        self.prepared = True
-        self.saved = None
+        super().__init__(net)
         self.taps = None
         self._w = {}
         self._consts = {}                 # input-size constants (shift masks): survive invalidate()
         self.planes = PlaneCache()
-        self.bufs = _Bufs()
-        self.bank = WeightBank()
-        self._bank_ready = False
 
     def invalidate(self):
+        super().invalidate()
         self._w = {}
         self.planes.clear()
-        self._bank_ready = False
 
-    def bucket_prefixes(self):
-        return [[""]]
+    def bank_entries(self):
+        net = self.net
+        for si, stage in enumerate(net.layers):
+            self.bank.conv(f"layers.{si}.conv", stage.conv.weight, stage.conv.bias, "c3")
+        self.bank.conv("conv_after_body", net.conv_after_body.weight, net.conv_after_body.bias, "c3")
+        self.bank.conv("conv_before_upsample.0", net.conv_before_upsample[0].weight, net.conv_before_upsample[0].bias, "c3")
+        for k, conv in enumerate(list(net.upsample.up)[0::2]):
+            self.bank.conv(f"upsample.up.{2 * k}", conv.weight, conv.bias, "c3")
 
     # ------------------------------------------------------------------ derived weights (cached until the weights change)
     def _pack(self, conv, cin_pad=None, cout_pad=None):
@@ -201,16 +202,7 @@ class GRLEngine:
         if H % net.pad_size or W % net.pad_size:
             raise NotImplementedError("GRL on libsrhip: training patches have to be multiples of the window / stripe size")
         dev = x3.device
-        if not self._bank_ready:
-            self.bank.begin()
-            for si, stage in enumerate(net.layers):
-                self.bank.conv(f"layers.{si}.conv", stage.conv.weight, stage.conv.bias, "c3")
-            self.bank.conv("conv_after_body", net.conv_after_body.weight, net.conv_after_body.bias, "c3")
-            self.bank.conv("conv_before_upsample.0", net.conv_before_upsample[0].weight, net.conv_before_upsample[0].bias, "c3")
-            for k, conv in enumerate(list(net.upsample.up)[0::2]):
-                self.bank.conv(f"upsample.up.{2 * k}", conv.weight, conv.bias, "c3")
-            self.bank.finish(dev)
-            self._bank_ready = True
+        self.ensure_prepared()
         t = Tape(self.bufs, self.bank, True, dev)
         nm = {id(p): k for k, p in net.named_parameters()}
         N = lambda p: None if p is None else nm[id(p)]
@@ -353,10 +345,3 @@ class GRLEngine:
         self.saved = (t, y)
         Bo, Ho, Wo = y.t.shape
         return y.t.view(Bo, 1, Ho, Wo)
-
-    def backward(self, dy, grads, need_dx=False, on_layer_done=None, grads_zeroed=False):
-        assert self.saved is not None, "backward() without a saved forward"
-        assert not need_dx, "GRL: no gradient with respect to the input image"
-        tape, out = self.saved
-        tape.backward(out, dy.reshape(out.t.shape).contiguous(), grads)
-        return None

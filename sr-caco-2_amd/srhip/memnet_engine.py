@@ -23,30 +23,30 @@ On the device (NHWC, T = B*H*W pixels):
 import torch
 
 from . import ops
-from .swinir_engine import _Bufs, bicubic_clamped
+from .engine import Engine
 
 CH = 64
 GEMM_BYTES_MAX = (1 << 31) - 1
 
 
-class MemNetEngine:
+class MemNetEngine(Engine):
+    need_dx_refusal = "MemNet (libsrhip): no gradient through the bicubic interpolation of the input"
+
     def __init__(self, net):
-        self.net = net
+        super().__init__(net)
         self.M = len(net.dense_memory_blocks)
         self.R = net.dense_memory_blocks[0].num_residual_blocks
-        self.bufs = _Bufs()
-        self.derived = _Bufs()
         self.ws = ops.WeightSet()
         if not (self.ws.use_bx3 and ops.bx3_nt_for(CH)):
             raise NotImplementedError("MemNet (libsrhip) runs on the bf16x3 kernels (SRHIP_MM=f32 is not supported)")
-        self._prep = self._prep_sig = None
-        self.prepared = False
-        self._eval_coefs = False
-        self.saved = None
+        self._eval_coefs = False        # the evaluation-time BatchNorm coefficients and folds are current (_prepare_eval_coefs)
+        self._fold_prep = None
+        self._h16_ready = False         # the gates' fp16-storage operands are laid out (_prepare_h16)
+        self._h16_overflow = False      # these weights left fp16's range on fp16 storage: evaluation stays on f32 storage
         self.bn = {k: m for k, m in net.named_modules() if isinstance(m, torch.nn.BatchNorm2d)}
 
     def invalidate(self):
-        self.prepared = False
+        super().invalidate()
         self._eval_coefs = False
         self._h16_ready = False
         self._h16_overflow = False
@@ -66,10 +66,8 @@ class MemNetEngine:
     def prepare(self):
         net, D, ws = self.net, self.derived, self.ws
         dev = net.reconstructor[2].weight.device
-        sig = tuple(p.data_ptr() for p in net.parameters())
-        rebuild = self._prep is None or sig != self._prep_sig
-        if rebuild:
-            tb = ops.PrepTable()
+
+        def fill(tb):
             for i in range(self.M):
                 mb = net.dense_memory_blocks[i]
                 for j in range(self.R):
@@ -79,8 +77,7 @@ class MemNetEngine:
                 gw = mb.gate_unit[2].weight.data.view(CH, self._gc(i))
                 tb.linear(gw, ws.planes(f"m{i}.gw", CH, self._gc(i), dev))
                 tb.linear(gw, ws.planes(f"m{i}.gwt", self._gc(i), CH, dev), transpose=True)
-            self._prep, self._prep_sig = tb.build(dev), sig
-        self._prep.run()
+        self.prep_table(fill)
         w3 = D.get("rec.w3", 1, CH, 3, 3, device=dev)           # 1x1 conv 64 -> 1 as the centre tap of a 3x3
         w3.zero_()
         w3[:, :, 1, 1].copy_(net.reconstructor[2].weight.data.view(1, CH))
@@ -113,10 +110,6 @@ class MemNetEngine:
         self._fold_prep.run()
         self._eval_coefs = True
 
-    def interpolate(self, x):
-        """network_memnet.py:127-139: [B,1,h,w] -> [B,s*h,s*w], bicubic (align_corners False), clamped."""
-        return bicubic_clamped(x, self.net.upscale)
-
     def _prepare_h16(self, dev):
         """the gate units' 1x1 convs as the centre tap of 3x3 weights, in the fp16x2 conv operand format (conv_h16.hip)"""
         tb = ops.PrepTable()
@@ -138,11 +131,9 @@ class MemNetEngine:
         dev = x.device
         if not self._eval_coefs:
             self._prepare_eval_coefs(dev)
-        if not getattr(self, "_h16_ready", False):
+        if not self._h16_ready:
             self._prepare_h16(dev)
-
-        def buf(name, *shape):
-            return self.bufs.get("h." + name, *shape, device=dev, dtype=torch.float16)
+        buf = self.bufs.tagged("h.", dev, torch.float16)
         a0 = self.bufs.get("h.a0", B, H, W, device=dev)
         ops.bn_apply(xi.view(-1, 1), D.d["coef.feature_extractor.0"], a0.view(-1, 1), relu=True)
         f0 = ops.conv3x3_cin1_h16(a0, net.feature_extractor[2].weight.data, None, CH, out=buf("f0", B, H, W, CH))
@@ -174,14 +165,13 @@ class MemNetEngine:
     def forward(self, x, dp=None, save=True):
         """x [B,h,w] (LR) -> [B,1,s*h,s*w].  BatchNorm follows ``net.training``: batch statistics (and the running-
         statistics update) in training mode, running statistics in eval mode."""
-        if not self.prepared:
-            self.prepare()
+        self.ensure_prepared()
         net, D, ws, R = self.net, self.derived, self.ws, self.R
         training = bool(net.training)
         assert not (save and not training), "MemNet (libsrhip): gradients in eval mode (frozen BatchNorm) are not built"
         if training:
             self._eval_coefs = False        # this forward updates the running statistics: the evaluation-time folds are stale
-        if not save and not training and ops.h16_eval() and self._h16_ok() and not getattr(self, "_h16_overflow", False):
+        if not save and not training and ops.h16_eval() and self._h16_ok() and not self._h16_overflow:
             # MemNet's memory blocks add 36 residual units per block without a normalisation in between: with untrained
             # statistics the feature maps leave fp16's range (65504).  One finiteness check of the output image per forward
             # (a 200-ms forward: the host round trip is noise); on overflow this net stays on f32 storage.
@@ -201,11 +191,8 @@ class MemNetEngine:
         dev = x.device
         if not training and not self._eval_coefs:
             self._prepare_eval_coefs(dev)
-        tag = "t" if save else "e"
         applied = {}
-
-        def buf(name, *shape):
-            return self.bufs.get(f"{tag}.{name}", *shape, device=dev)
+        buf = self.bufs.tagged("t." if save else "e.", dev)
 
         def scr(key):
             return self.bufs.get(key, B, H, W, CH, device=dev)
@@ -292,17 +279,13 @@ class MemNetEngine:
 
     # ------------------------------------------------------------------ backward
     def backward(self, dy, grads, need_dx=False, on_layer_done=None, grads_zeroed=False):
-        sv = self.saved
-        assert sv is not None, "backward() without a saved forward"
-        assert not need_dx, "MemNet (libsrhip): no gradient through the bicubic interpolation of the input"
+        sv = self.saved_for_backward(need_dx)
         net, D, ws, R = self.net, self.derived, self.ws, self.R
         B, H, W = sv["B"], sv["H"], sv["W"]
         T = B * H * W
         dev = dy.device
         touched = set()
-
-        def buf(name, *shape):
-            return self.bufs.get("g." + name, *shape, device=dev)
+        buf = self.bufs.tagged("g.", dev)
 
         def bn_bwd(pre, dz, x, coef, a=None, dx=None, res=None):
             ops.bn_bwd(dz, x, coef, a=a, dx=dx, res=res, dgamma=grads[pre + ".weight"], dbeta=grads[pre + ".bias"],

@@ -19,7 +19,7 @@ import math
 import torch
 
 from . import ops
-from .swinir_engine import _Bufs
+from .engine import Engine
 
 CH = 64
 SLOPE = 0.2
@@ -45,23 +45,17 @@ def _convT_maps(ci, co, device):
     return src.clamp_min(0).to(device), valid.to(device), pos.to(device)
 
 
-class MSLapSRNEngine:
+class MSLapSRNEngine(Engine):
+    need_dx_refusal = "MSLapSRN (libsrhip): no gradient with respect to the input image"
+
     def __init__(self, net):
-        self.net = net
+        super().__init__(net)
         self.octaves = int(math.log2(net.upscale))
-        self.bufs = _Bufs()
-        self.derived = _Bufs()
         self.ws = ops.WeightSet()
         if not (self.ws.use_bx3 and ops.bx3_nt_for(CH) and ops.ps2_fusable(CH, 4 * CH)):
             raise NotImplementedError("MSLapSRN (libsrhip) runs on the bf16x3 kernels (SRHIP_MM=f32 is not supported)")
-        self._prep = self._prep_sig = None
         self._maps = None
-        self.prepared = False
-        self.saved = None
         self.intermediate_outs = []
-
-    def invalidate(self):
-        self.prepared = False
 
     def bucket_prefixes(self):
         """0.4-1.2 M parameters: one gradient bucket."""
@@ -81,9 +75,6 @@ class MSLapSRNEngine:
         if self._maps is None:
             self._maps = (_convT_maps(CH, CH, dev), _convT_maps(1, 1, dev))
         (srcF, validF, _), (src1, valid1, _) = self._maps
-        sig = tuple(p.data_ptr() for p in self.net.parameters())
-        rebuild = self._prep is None or sig != self._prep_sig
-        tb = ops.PrepTable() if rebuild else None
         for o in range(self.octaves):
             a, b, _ = self._mods(o)
             # dense 3x3 forms of the two transposed convs (+ biases repeated over the 4 sub-pixels)
@@ -94,13 +85,14 @@ class MSLapSRNEngine:
             w4.view(-1).copy_(torch.where(valid1, b.weight.data.reshape(-1)[src1], w4.new_zeros(())))
             D.get(f"o{o}.b4", 4, device=dev).copy_(b.bias.data.repeat_interleave(4))
             D.get(f"o{o}.w4f", 1, 4, 3, 3, device=dev).copy_(w4.flip(2, 3).reshape(1, 4, 3, 3))
-            if rebuild:
+
+        def fill(tb):
+            for o in range(self.octaves):
+                a = self._mods(o)[0]
                 for k in range(10):
                     tb.conv_pair(f"o{o}.c{k}", a[k].cl[0].weight.data, ws)
-                tb.conv_pair(f"o{o}.up", wc, ws, ps2=True)
-        if rebuild:
-            self._prep, self._prep_sig = tb.build(dev), sig
-        self._prep.run()
+                tb.conv_pair(f"o{o}.up", D.d[f"o{o}.wc"], ws, ps2=True)
+        self.prep_table(fill)
         self.prepared = True
 
     def forward_h16(self, x):
@@ -109,9 +101,7 @@ class MSLapSRNEngine:
         net, D, ws = self.net, self.derived, self.ws
         B, h, w = x.shape
         dev = x.device
-
-        def buf(name, *shape):
-            return self.bufs.get("h." + name, *shape, device=dev, dtype=torch.float16)
+        buf = self.bufs.tagged("h.", dev, torch.float16)
         feat = ops.conv3x3_cin1_h16(x, net.conv1[0].weight.data, net.conv1[0].bias.data, CH, out=buf("f0", B, h, w, CH), leaky=SLOPE)
         img, outs = x, []
         for o in range(self.octaves):
@@ -139,19 +129,14 @@ class MSLapSRNEngine:
     # ------------------------------------------------------------------ forward
     def forward(self, x, dp=None, save=True):
         """x [B,H,W] (LR) -> [B,1,s*H,s*W]; the images of the earlier octaves in self.intermediate_outs."""
-        if not self.prepared:
-            self.prepare()
+        self.ensure_prepared()
         if not save and ops.h16_eval() and self._h16_ok():
             self.last_eval_path = "fp16 storage"
             return self.forward_h16(x)
         net, D, ws = self.net, self.derived, self.ws
         B, h, w = x.shape
         dev = x.device
-        tag = "t" if save else "e"
-
-        def buf(name, *shape):
-            return self.bufs.get(f"{tag}.{name}", *shape, device=dev)
-
+        buf = self.bufs.tagged("t." if save else "e.", dev)
         feat = buf("f0", B, h, w, CH)
         ops.conv3x3_cin1_fwd(x, net.conv1[0].weight.data, net.conv1[0].bias.data, CH, out=feat)
         ops.leaky_relu_(feat, SLOPE)
@@ -190,16 +175,12 @@ class MSLapSRNEngine:
     def backward(self, dy, grads, need_dx=False, on_layer_done=None, grads_zeroed=False, d_inter=None):
         """dy: gradient of the output [B,1,sH,sW]; d_inter: gradients of intermediate_outs (list, entries may be
         None) -- the trainer's multi-scale loss (model_plain.py:277-314)."""
-        sv = self.saved
-        assert sv is not None, "backward() without a saved forward"
-        assert not need_dx, "MSLapSRN (libsrhip): no gradient with respect to the input image"
+        sv = self.saved_for_backward(need_dx)
         net, D, ws = self.net, self.derived, self.ws
         B = sv["B"]
         dev = dy.device
         (_, _, posF), (_, _, pos1) = self._maps
-
-        def buf(name, *shape):
-            return self.bufs.get("g." + name, *shape, device=dev)
+        buf = self.bufs.tagged("g.", dev)
 
         g_img = None        # gradient wrt the octave's image arriving from the NEXT octave's image branch
         g_feat = None       # gradient wrt the octave's features arriving from the NEXT octave's first conv

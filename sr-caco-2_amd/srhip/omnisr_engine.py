@@ -8,8 +8,7 @@ from kernels of this library."""
 import torch
 
 from . import ops
-from .swinir_engine import _Bufs
-from .tape import Tape, WeightBank
+from .tape import Tape, TapeEngine
 
 
 def _w2(conv):
@@ -21,25 +20,25 @@ def _b(m):
     return None if m.bias is None else m.bias.data
 
 
-class OmniSREngine:
-    train_graph_default = True      # ModelPlain replays the training step from a hipGraph (TrainStep.step_graph)
+class OmniSREngine(TapeEngine):
+    """``prepared``: the tape graph's bank; the evaluation forward prepares nothing (its bias images: ``_bias``)."""
+    need_dx_refusal = "OmniSR: no gradient with respect to the input image"
 
     def __init__(self, net):
-        self.net = net
-        self.prepared = True
-        self.saved = None
+        super().__init__(net)
         self.taps = None
         self._bias = {}
-        self.bufs = _Bufs()
-        self.bank = WeightBank()
-        self._bank_ready = False
 
     def invalidate(self):
+        super().invalidate()
         self._bias = {}
-        self._bank_ready = False
 
-    def bucket_prefixes(self):
-        return [[""]]
+    def bank_entries(self):
+        net = self.net
+        self.bank.conv("output", net.output.weight, net.output.bias, "c3")
+        self.bank.conv("up.0", net.up[0].weight, net.up[0].bias, "c3")
+        for g, osag in enumerate(net.residual_layer):
+            self.bank.conv(f"esa{g}.conv3", osag.esa.conv3.weight, osag.esa.conv3.bias, "c3")
 
     # ------------------------------------------------------------------ pieces (x NHWC [B, H, W, C])
     @staticmethod
@@ -199,14 +198,7 @@ class OmniSREngine:
             raise NotImplementedError("OmniSR on libsrhip: training patches have to be multiples of the 8-pixel window")
         X, Y = H // ws, W // ws
         P = B * H * W
-        if not self._bank_ready:
-            self.bank.begin()
-            self.bank.conv("output", net.output.weight, net.output.bias, "c3")
-            self.bank.conv("up.0", net.up[0].weight, net.up[0].bias, "c3")
-            for g, osag in enumerate(net.residual_layer):
-                self.bank.conv(f"esa{g}.conv3", osag.esa.conv3.weight, osag.esa.conv3.bias, "c3")
-            self.bank.finish(x3.device)
-            self._bank_ready = True
+        self.ensure_prepared()
         t = Tape(self.bufs, self.bank, True, x3.device)
         nm = {id(p): k for k, p in net.named_parameters()}
         N = lambda p: None if p is None else nm[id(p)]
@@ -318,10 +310,3 @@ class OmniSREngine:
         y = t.reshape(t.shuffle(u, s), B, H * s, W * s)
         self.saved = (t, y)
         return y.t.view(B, 1, H * s, W * s)
-
-    def backward(self, dy, grads, need_dx=False, on_layer_done=None, grads_zeroed=False):
-        assert self.saved is not None, "backward() without a saved forward"
-        assert not need_dx, "OmniSR: no gradient with respect to the input image"
-        tape, out = self.saved
-        tape.backward(out, dy.reshape(out.t.shape).contiguous(), grads)
-        return None

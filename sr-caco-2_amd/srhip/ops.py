@@ -271,26 +271,6 @@ class WeightSet:
         return self.d[key]
 
 
-def prepare_conv_packs(eng, convs):
-    """prepare() of an engine whose derived weights are the packs of its 3x3 convs, ``convs`` an iterable of (name, weight
-    [Co,Ci,3,3], ps2) -- read only when the packs are laid out, so a generator costs a steady-state step nothing.  Planes:
-    one job table, built when first needed and again when a parameter of eng.net moved (data_ptr), otherwise only re-run;
-    exact-f32 kernels: the packs in eng.derived."""
-    ws = eng.ws
-    if ws.use_bx3:
-        sig = tuple(p.data_ptr() for p in eng.net.parameters())
-        if eng._prep is None or sig != eng._prep_sig:
-            tb = PrepTable()
-            for name, w, ps2 in convs:
-                tb.conv_pair(name, w, ws, ps2=ps2)
-            eng._prep, eng._prep_sig = tb.build(w.device), sig
-        eng._prep.run()
-    else:
-        for name, w, _ in convs:
-            ws.pack_conv(name, w, eng.derived)
-    eng.prepared = True
-
-
 def gemm_nt(A, W, bias=None, out=None, a_mode=0, ln_stats=None, epi=0, R=None,
             rowscale=None, rows_per_scale=1, alpha=1.0, aux=None, stats_out=None):
     """out[M,N] = epi(pro(A)[M,K] . W[N,K]^T + bias).  W: f32 tensor (exact-f32

@@ -11,25 +11,24 @@ convs directly on [T x C]; ReLU is the GEMM epilogue, its mask the epilogue of t
 import torch
 
 from . import ops
-from .swinir_engine import _Bufs
+from .engine import Engine
 
 C1, C2, KP1 = 1024, 128, 28      # channels; padded taps of the 5x5 layer
 
 
-class SRCNNEngine:
+class SRCNNEngine(Engine):
+    need_dx_refusal = "SRCNN (libsrhip): no gradient with respect to the interpolated input"
+
     def __init__(self, net):
-        self.net = net
-        self.bufs = _Bufs()
-        self.derived = _Bufs()
+        super().__init__(net)
         self.ws = ops.WeightSet()
         self.ws.use_bx3 = True
-        self._prep = self._prep_sig = None
-        self.prepared = False
-        self.saved = None
+        self._h16_ready = False         # the fp16-storage operands of these weights are laid out (_prepare_h16)
+        self._h16_w1 = self._h16_w2 = None
         self.rows_max = ((1 << 29) - 1) // C1      # rows of a 1024-wide operand one GEMM call addresses (32-bit element offsets)
 
     def invalidate(self):
-        self.prepared = False
+        super().invalidate()
         self._h16_ready = False
 
     def bucket_prefixes(self):
@@ -40,20 +39,20 @@ class SRCNNEngine:
         dev = net.map[0].weight.device
         w1p = D.get("w1p", C1, KP1, device=dev)          # [1024][25] taps + 3 zero columns
         w3p = D.get("w3p", 4, C2, device=dev)            # [1][128] + 3 zero rows
-        sig = tuple(p.data_ptr() for p in net.parameters())
-        if self._prep is None or sig != self._prep_sig:
+
+        def fill(tb):
             w1p.zero_()
             w3p.zero_()
-            tb = ops.PrepTable()
             tb.linear(w1p, ws.planes("w1", C1, KP1, dev))
             tb.linear(net.map[0].weight.data.view(C2, C1), ws.planes("w2", C2, C1, dev))
             tb.linear(net.map[0].weight.data.view(C2, C1), ws.planes("w2T", C1, C2, dev), transpose=True)
             tb.linear(w3p, ws.planes("w3", 4, C2, dev))
             tb.linear(w3p, ws.planes("w3T", C2, 4, dev), transpose=True)
-            self._prep, self._prep_sig = tb.build(dev), sig
-        w1p[:, :25].copy_(net.features[0].weight.data.view(C1, 25))
-        w3p[:1].copy_(net.reconstruction.weight.data.view(1, C2))
-        self._prep.run()
+
+        def copies():
+            w1p[:, :25].copy_(net.features[0].weight.data.view(C1, 25))
+            w3p[:1].copy_(net.reconstruction.weight.data.view(1, C2))
+        self.prep_table(fill, before_run=copies)
         self.prepared = True
 
     def _prepare_h16(self, dev):
@@ -93,20 +92,15 @@ class SRCNNEngine:
 
     def forward(self, x, dp=None, save=True):
         """x [B,H,W] (already at the target size) -> [B,1,H,W]."""
-        if not self.prepared:
-            self.prepare()
-        if not save and ops.h16_eval() and (getattr(self, "_h16_ready", False) or self._prepare_h16(x.device)):
+        self.ensure_prepared()
+        if not save and ops.h16_eval() and (self._h16_ready or self._prepare_h16(x.device)):
             self.last_eval_path = "fp16 storage"
             return self.forward_h16(x)
         net, D, ws = self.net, self.derived, self.ws
         B, H, W = x.shape
         T = B * H * W
         dev = x.device
-        tag = "t" if save else "e"
-
-        def buf(name, *shape):
-            return self.bufs.get(f"{tag}.{name}", *shape, device=dev)
-
+        buf = self.bufs.tagged("t." if save else "e.", dev)
         b3 = D.get("b3p", 4, device=dev)
         b3.zero_()
         b3[:1].copy_(net.reconstruction.bias.data)
@@ -131,17 +125,12 @@ class SRCNNEngine:
         return y.view(B, 1, H, W)
 
     def backward(self, dy, grads, need_dx=False, on_layer_done=None, grads_zeroed=False):
-        sv = self.saved
-        assert sv is not None, "backward() without a saved forward"
-        assert not need_dx, "SRCNN (libsrhip): no gradient with respect to the interpolated input"
+        sv = self.saved_for_backward(need_dx)
         net, D, ws = self.net, self.derived, self.ws
         B, H, W = sv["B"], sv["H"], sv["W"]
         T = B * H * W
         dev = dy.device
-
-        def buf(name, *shape):
-            return self.bufs.get("g." + name, *shape, device=dev)
-
+        buf = self.bufs.tagged("g.", dev)
         dy4 = buf("dy4", T, 4)
         dy4.zero_()
         dy4[:, 0].copy_(dy.reshape(T))

@@ -17,49 +17,20 @@ backward = 4 data-gradient GEMMs + 4 weight-gradient GEMMs (+ slice reducers)
 import os
 
 import torch
-import torch.nn.functional as F
 
 from . import ops
-
-
-class _Bufs:
-    """Persistent activation / gradient buffers keyed by name (no allocation in
-    the steady-state step; also what makes the step graph-capturable)."""
-
-    def __init__(self):
-        self.d = {}
-
-    def get(self, key, *shape, device="cuda", dtype=torch.float32):
-        t = self.d.get(key)
-        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
-            if t is not None:
-                ops.note_realloc()      # a replaced buffer is freed: captured graphs holding its address must be re-made
-            t = torch.empty(shape, device=device, dtype=dtype)
-            self.d[key] = t
-        return t
-
-    def clear(self):
-        if self.d:
-            ops.note_realloc()
-        self.d.clear()
-
-
-def bicubic_clamped(x, scale):
-    """[B,1,h,w] -> [B,s*h,s*w]: the bicubic interpolation (align_corners False), clamped to [0, 1], in front of the nets
-    that refine an interpolated input (VDSR, DRRN, MemNet, DSR-Splines) -- stock PyTorch-ROCm, as in the reference."""
-    out = F.interpolate(x, size=(scale * x.shape[2], scale * x.shape[3]), mode='bicubic', align_corners=False)
-    return torch.clamp(out, min=0.0, max=1.0)[:, 0].contiguous()
+from .engine import Engine
 
 
 def net_dev(net):
     return net.conv_first.weight.device
 
 
-class SwinIREngine:
-    train_graph_default = True      # ModelPlain replays the training step from a hipGraph (TrainStep.step_graph)
+class SwinIREngine(Engine):
+    train_graph_default = True
 
     def __init__(self, net):
-        self.net = net
+        super().__init__(net)
         self.C = net.embed_dim
         self.hid = int(net.embed_dim * net.mlp_ratio)
         self.scale = net.upscale
@@ -79,12 +50,9 @@ class SwinIREngine:
         for li, layer in enumerate(net.layers):
             for _ in layer.residual_group.blocks:
                 self.layer_of_block.append(li)
-        self.bufs = _Bufs()
-        self.derived = _Bufs()
         self.ws = ops.WeightSet()      # matmul operands: f32 tensors or bf16x3 planes
-        self._prep = self._prep_sig = None
-        self.prepared = False
-        self.saved = None
+        self.wstream = None            # the weight gradients' side stream (backward)
+        self._tail_planes, self.prepared_tail = None, False
         # The MLP half of a block as one kernel per direction on the Linear GEMMs' own two-plane fp16 operands (mlp_f16.hip; no extra weight planes): one
         # A fetch and one epilogue per direction instead of two, the hidden activation never read back.  SRHIP_MLP_F16=0:
         # the separate Linear launches.
@@ -147,9 +115,6 @@ class SwinIREngine:
         return list(range(lo, nb)), list(range(1, lo)), [0]
 
     # ------------------------------------------------------------------ weights
-    def invalidate(self):
-        self.prepared = False
-
     def prepare(self):
         """Derived weight copies (folded LayerNorm, transposes, conv packs, dense
         bias images).  Must be re-run whenever parameters change."""
@@ -185,12 +150,11 @@ class SwinIREngine:
         """bf16x3 planes of every matmul operand + folded biases + bias images, by ONE
         launch over a job table built once (rebuilt if a parameter moved)."""
         net, C, hid, D, ws = self.net, self.C, self.hid, self.derived, self.ws
-        sig = tuple(p.data_ptr() for p in net.parameters())
         if self.conv3:
             self._refresh_conv3(net.conv_first.weight.device)
-        if self._prep is None or sig != self._prep_sig:
+
+        def fill(tb):
             dev = net.conv_first.weight.device
-            tb = ops.PrepTable()
             for i, b in enumerate(self.blocks):
                 g1, g2 = b.norm1.weight.data, b.norm2.weight.data
                 wq, wp = b.attn.qkv.weight.data, b.attn.proj.weight.data
@@ -219,8 +183,7 @@ class SwinIREngine:
                 for name, _, _ in self._rconvs():
                     tb.linear(D.d[name + ".w1p"], ws.planes(name + ".1.w", P, P, dev))
                     tb.linear(D.d[name + ".w1p"], ws.planes(name + ".1.wT", P, P, dev), transpose=True)
-            self._prep, self._prep_sig = tb.build(dev), sig
-        self._prep.run()
+        self.prep_table(fill)
 
     def _prepare_f32(self):
         net, C, hid, D = self.net, self.C, self.hid, self.derived
@@ -314,7 +277,7 @@ class SwinIREngine:
 
     def _eval_tail_planes(self, dev):
         """the 'pixelshuffle' upsampler's convs in sub-pixel-major column order (PrepTable.conv(ps2=True)): evaluation only"""
-        if getattr(self, "_tail_planes", None) is None or not self.prepared_tail:
+        if self._tail_planes is None or not self.prepared_tail:
             tb = ops.PrepTable()
             nf = self.net.num_feat
             self._tail_planes = []
@@ -330,18 +293,14 @@ class SwinIREngine:
     def forward(self, x, dp=None, save=True):
         """x: [B,H,W] fp32 cuda (in_chans 1) or NHWC [B,H,W,4] (in_chans 2..4, zero-padded), H and W multiples of 8
         -> [B,in_chans,s*H,s*W].  dp: None or a [2*nblocks, B] tensor of DropPath multipliers."""
-        if not self.prepared:
-            self.prepare()
+        self.ensure_prepared()
         net, C, hid, D, ws = self.net, self.C, self.hid, self.derived, self.ws
         B, H, W = x.shape[:3]
         assert x.dim() == (3 if self.ci == 1 else 4) and (self.ci == 1 or x.shape[3] == 4), x.shape
         T = B * H * W
         dev = x.device
         bufs = self.bufs
-        tag = "t" if save else "e"    # eval shares one set of block buffers
-
-        def buf(name, *shape):
-            return bufs.get(f"{tag}.{name}", *shape, device=dev)
+        buf = bufs.tagged("t." if save else "e.", dev)    # eval shares one set of block buffers
 
         def resi_conv(name, mod, key, src, dst, skip):
             """dst = conv(src) + skip, the conv being '1conv' or '3conv'; returns what the backward needs."""
@@ -531,8 +490,7 @@ class SwinIREngine:
     def backward(self, dy, grads, need_dx=False, on_layer_done=None, grads_zeroed=False):
         """dy: [B,in_chans,s*H,s*W]; grads: dict name -> tensor to receive the parameter
         gradient (overwritten).  Returns d loss / d x in the layout forward() took if need_dx."""
-        sv = self.saved
-        assert sv is not None, "backward() without a saved forward"
+        sv = self.saved_for_backward()
         net, C, hid, D, ws = self.net, self.C, self.hid, self.derived, self.ws
         B, H, W, dp = sv["B"], sv["H"], sv["W"], sv["dp"]
         T = B * H * W
@@ -540,9 +498,7 @@ class SwinIREngine:
         bufs = self.bufs
         r = self.scale
         cu = r * r * net.in_chans
-
-        def buf(name, *shape):
-            return bufs.get("g." + name, *shape, device=dev)
+        buf = bufs.tagged("g.", dev)
 
         def G(name):
             return grads[name]
@@ -650,7 +606,7 @@ class SwinIREngine:
         # chain (no weight gradient is on that chain).  Their operands then outlive the layer: two sets of the per-layer
         # buffers, by layer parity (+1.3 GB).
         side_on = defer and dev.type == "cuda" and os.environ.get("SRHIP_SWIN_SIDE_WGRAD", "1") == "1"
-        if side_on and getattr(self, "wstream", None) is None:
+        if side_on and self.wstream is None:
             self.wstream = torch.cuda.Stream(device=dev)
         main_stream = torch.cuda.current_stream() if dev.type == "cuda" else None
 

@@ -7,29 +7,16 @@ back through the index; roll / window partition / reverse are the relayout copie
 Slower than the fused engine by design (nothing is fused); the same kernels' parity."""
 import math
 
-import torch
-
-from . import ops
-from .swinir_engine import _Bufs
-from .tape import Tape, WeightBank
+from .tape import Tape, TapeEngine
 
 
-class SwinIRTapeEngine:
-    train_graph_default = True      # ModelPlain replays the training step from a hipGraph (TrainStep.step_graph)
+class SwinIRTapeEngine(TapeEngine):
+    need_dx_refusal = "SwinIR (tape graph): no gradient with respect to the input image"
+    need_dx_error = NotImplementedError
 
     def __init__(self, net):
-        self.net = net
-        self.bufs = _Bufs()
-        self.bank = WeightBank()
-        self.prepared = False
-        self.saved = None
+        super().__init__(net)
         self._masks = {}
-
-    def invalidate(self):
-        self.prepared = False
-
-    def bucket_prefixes(self):
-        return [[""]]
 
     def _convs(self):
         net = self.net
@@ -50,19 +37,15 @@ class SwinIRTapeEngine:
             out += [(f"upsample.{2 * i}", net.upsample[2 * i]) for i in range(int(round(math.log2(net.upscale))))]
         return out
 
-    def prepare(self):
-        self.bank.begin()
+    def bank_entries(self):
         for key, m in self._convs():
             self.bank.conv(key, m.weight, m.bias, "c3")
-        self.bank.finish(self.net.conv_first.weight.device)
-        self.prepared = True
 
     def forward(self, x, dp=None, save=True):
         """x [B, H, W] (1 channel) or NHWC [B, H, W, 4] (in_chans 2..4 zero-padded, as SwinIR.prepare_input hands it over), H and
         W multiples of the window -> [B, in_chans, s H, s W]; dp: None or [2 nblocks, B] DropPath multipliers."""
         from dlib.models.network_swinir import _shift_mask
-        if not self.prepared:
-            self.prepare()
+        self.ensure_prepared()
         net = self.net
         B, H, W = x.shape[:3]
         ci = net.in_chans
@@ -180,11 +163,3 @@ class SwinIRTapeEngine:
         if save:
             self.saved = (t, y)
         return y.t.reshape(B, ci, H * s, W * s)
-
-    def backward(self, dy, grads, need_dx=False, on_layer_done=None, grads_zeroed=False):
-        assert self.saved is not None, "backward() without a saved forward"
-        if need_dx:
-            raise NotImplementedError("SwinIR (tape graph): no gradient with respect to the input image")
-        tape, out = self.saved
-        tape.backward(out, dy.reshape(out.t.shape).contiguous(), grads)
-        return None

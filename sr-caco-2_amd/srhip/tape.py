@@ -27,7 +27,7 @@ import torch
 
 from . import ops
 from ._lib import call
-from .swinir_engine import _Bufs
+from .engine import Bufs, Engine
 
 
 def _p(t):
@@ -211,7 +211,7 @@ class WeightBank:
 
     def __init__(self):
         self.d = {}
-        self.bufs = _Bufs()
+        self.bufs = Bufs()
         self.ws = ops.WeightSet()
         self._jobs, self._table, self._sig = [], None, None
 
@@ -290,7 +290,7 @@ class Tape:
         self.seed, self._site = None, 0      # dropout: the step's seed tensor (the engine sets it) and the next site number
         self.pool = None
         if save:
-            if getattr(bufs, "pool", None) is None:
+            if bufs.pool is None:
                 bufs.pool = _Pool()
             self.pool = bufs.pool
             self.pool.reset()
@@ -1584,24 +1584,21 @@ class Tape:
                 gt.zero_()
 
 
-class TapeEngine:
+class TapeEngine(Engine):
     """Base of the engines written as a tape graph: subclasses implement bank_entries() (which convs exist, in which
-    form) and graph(tape, x3) -> output Var ([B, H, W] image)."""
-    train_graph_default = True      # ModelPlain replays the training step from a hipGraph (TrainStep.step_graph)
+    form) and graph(tape, x3) -> output Var ([B, H, W] image), or a forward() of their own that leaves (tape, output Var)
+    in ``saved``.  One gradient bucket; no gradient of the input."""
+    train_graph_default = True
+    need_dx_refusal = "tape engines: no gradient with respect to the input image"
 
     def __init__(self, net):
-        self.net = net
-        self.bufs = _Bufs()
+        super().__init__(net)
         self.bank = WeightBank()
-        self.prepared = False
-        self.saved = None
+        self._h16_ready, self._h16_up = False, []       # edsr_body_h16: the upsampler's fp16-storage operands are laid out
 
     def invalidate(self):
-        self.prepared = False
+        super().invalidate()
         self._h16_ready = False
-
-    def bucket_prefixes(self):
-        return [[""]]           # one gradient bucket: every parameter
 
     def prepare(self):
         self.bank.begin()
@@ -1611,8 +1608,7 @@ class TapeEngine:
 
     def forward(self, x, dp=None, save=True):
         """x [B, H, W] -> [B, 1, s H, s W]."""
-        if not self.prepared:
-            self.prepare()
+        self.ensure_prepared()
         if not save and ops.h16_eval() and hasattr(self, "forward_h16") and self._h16_ok():
             self.last_eval_path = "fp16 storage (attention blocks f32)"
             return self.forward_h16(x)
@@ -1632,7 +1628,7 @@ class TapeEngine:
         net, bank = self.net, self.bank
         F, rs = net.n_feats, float(net.res_scale)
         dev = x.device
-        if not getattr(self, "_h16_ready", False):        # the upsampler convs whole, in sub-pixel-major column order
+        if not self._h16_ready:        # the upsampler convs whole, in sub-pixel-major column order
             tb = ops.PrepTable()
             self._h16_up = []
             for st in range(int(math.log2(net.upscale))):
@@ -1664,8 +1660,6 @@ class TapeEngine:
         return y.view(B, 1, H, W)
 
     def backward(self, dy, grads, need_dx=False, on_layer_done=None, grads_zeroed=False):
-        assert self.saved is not None, "backward() without a saved forward"
-        assert not need_dx, "tape engines: no gradient with respect to the input image"
-        tape, out = self.saved
+        tape, out = self.saved_for_backward(need_dx)
         tape.backward(out, dy.reshape(out.t.shape).contiguous(), grads)
         return None

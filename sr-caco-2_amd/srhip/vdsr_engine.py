@@ -10,36 +10,26 @@ epilogue, the ReLU mask of the backward as the data-gradient conv's epilogue (ep
 import torch
 
 from . import ops
-from .swinir_engine import _Bufs, bicubic_clamped
+from .engine import Engine
 
 CH = 64
 
 
-class VDSREngine:
+class VDSREngine(Engine):
+    need_dx_refusal = "VDSR (libsrhip): no gradient through the bicubic interpolation of the input"
+
     def __init__(self, net):
-        self.net = net
+        super().__init__(net)
         self.nt = len(net.trunk)
-        self.bufs = _Bufs()
-        self.derived = _Bufs()
         self.ws = ops.WeightSet()
         self.ws.use_bx3 = ops.bx3_nt_for(CH)
-        self._prep = self._prep_sig = None
-        self.prepared = False
-        self.saved = None
-
-    def invalidate(self):
-        self.prepared = False
 
     def bucket_prefixes(self):
         """0.67 M parameters: one gradient bucket."""
         return [["conv1.", "trunk.", "conv2."]]
 
     def prepare(self):
-        ops.prepare_conv_packs(self, ((f"t{k}", self.net.trunk[k].conv.weight.data, False) for k in range(self.nt)))
-
-    def interpolate(self, x):
-        """network_vdsr.py:78-90: [B,1,h,w] -> [B,s*h,s*w], bicubic (align_corners False), clamped."""
-        return bicubic_clamped(x, self.net.upscale)
+        self.prepare_conv_packs((f"t{k}", self.net.trunk[k].conv.weight.data, False) for k in range(self.nt))
 
     def forward_h16(self, x):
         """--amp evaluation on fp16 storage (conv_h16.hip): the same launches with float16 feature maps, one fp16 product."""
@@ -57,8 +47,7 @@ class VDSREngine:
 
     def forward(self, x, dp=None, save=True):
         """x [B,H,W] (LR) -> [B,1,s*H,s*W]."""
-        if not self.prepared:
-            self.prepare()
+        self.ensure_prepared()
         if not save and ops.h16_eval() and self.ws.use_bx3 and self.ws["t0.wp"].fmt == 1:
             self.last_eval_path = "fp16 storage"
             return self.forward_h16(x)
@@ -66,11 +55,7 @@ class VDSREngine:
         xi = self.interpolate(x[:, None])
         B, H, W = xi.shape
         dev = x.device
-        tag = "t" if save else "e"
-
-        def buf(name, *shape):
-            return self.bufs.get(f"{tag}.{name}", *shape, device=dev)
-
+        buf = self.bufs.tagged("t." if save else "e.", dev)
         a = buf("a0", B, H, W, CH)
         ops.conv3x3_cin1_fwd(xi, net.conv1[0].weight.data, None, CH, out=a, relu=True)
         acts = [a]
@@ -88,17 +73,12 @@ class VDSREngine:
         return y.view(B, 1, H, W)
 
     def backward(self, dy, grads, need_dx=False, on_layer_done=None, grads_zeroed=False):
-        sv = self.saved
-        assert sv is not None, "backward() without a saved forward"
-        assert not need_dx, "VDSR (libsrhip): no gradient through the bicubic interpolation of the input"
+        sv = self.saved_for_backward(need_dx)
         net = self.net
         B, H, W = sv["B"], sv["H"], sv["W"]
         dev = dy.device
         acts = sv["acts"]
-
-        def buf(name, *shape):
-            return self.bufs.get("g." + name, *shape, device=dev)
-
+        buf = self.bufs.tagged("g.", dev)
         dy = dy.reshape(B, H, W).contiguous()
         # conv2 (64 -> 1): weight gradient = the 1-channel kernel with x / dy swapped and flipped taps,
         # data gradient = the 1-channel forward kernel with flipped taps; then the last ReLU's mask

@@ -108,7 +108,7 @@ def test_tape_dropout_in_a_small_graph_vs_float64():
     Linear's GEMM (tests/test_gpu_kernels.py: gemm_nt; CONTRACTION of tests/test_gpu_tape_op_kernels.py).  A second run of the
     graph, and a second launch of a site's backward, reproduce the first bit for bit: masks are regenerated, not consumed."""
     from srhip import ops
-    from srhip.swinir_engine import _Bufs
+    from srhip.engine import Bufs
     from srhip.tape import Tape, WeightBank
     p, M = 0.25, 40
     gen = torch.Generator().manual_seed(17)
@@ -118,7 +118,7 @@ def test_tape_dropout_in_a_small_graph_vs_float64():
     dy = torch.randn(M, 144, generator=gen)
     par = {k: torch.nn.Parameter(v.cuda()) for k, v in (("W1", W1), ("b1", b1), ("W2", W2), ("b2", b2))}
     seed = torch.tensor([SEED], dtype=torch.int64, device="cuda")
-    bufs, bank = _Bufs(), WeightBank()
+    bufs, bank = Bufs(), WeightBank()
 
     def run():
         t = Tape(bufs, bank, True, torch.device("cuda"))
@@ -161,13 +161,13 @@ def test_tape_dropout_mask_does_not_depend_on_the_slicing(monkeypatch):
     """Tape._dropout walks a tensor LIMIT elements at a time and passes each slice's offset: with the limit lowered to 1000
     (slices of 1000 elements: multiples of 4) the output is the one launch's"""
     from srhip import tape as T
-    from srhip.swinir_engine import _Bufs
+    from srhip.engine import Bufs
     seed = torch.tensor([SEED], dtype=torch.int64, device="cuda")
     x = torch.randn(37, 144, generator=torch.Generator().manual_seed(3)).cuda()
     outs = []
     for limit in (T.LIMIT, 1003):
         monkeypatch.setattr(T, "LIMIT", limit)
-        t = T.Tape(_Bufs(), T.WeightBank(), False, torch.device("cuda"))
+        t = T.Tape(Bufs(), T.WeightBank(), False, torch.device("cuda"))
         t.seed = seed
         outs.append(t.dropout(t.var(x, need=False), 0.25).t.clone())
     assert torch.equal(outs[0], outs[1])
