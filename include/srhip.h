@@ -918,6 +918,36 @@ int srhip_metrics_ssim(const float* E, const float* Hh, int B, int H, int W, int
                        const int* thresholds_dev, int nth, int inputs_are_u8, double* workspace,
                        float* out, void* stream);
 
+/* ---- metrics at the white level L (255 .. 65535; normally the set's in_max): --metric_levels.  Not reference calls: the
+ *      reference's metrics are the 8-bit ones above.  The three rules they share:
+ *   Q_L(x) = clamp(rint_half_even(float32(clamp(x, 0, 1)) * float32(L)), 0, L): ONE float32 product, the rule of
+ *     srhip_emit_uint and of tensor2uint82float (L = 255);
+ *   the ROI of slot k stays defined at the 8-bit levels, roi = Q_255(H) >= th_k with thresholds in 0 .. 256, so it is the pixel
+ *     set of the 8-bit sweep and of the crop samplers whatever L is; with inputs_are_levels the 8-bit level of a level v is
+ *     Q_255(np.float32(v / L)), the quotient in double and rounded once (srhip_levels_u16_to_u8's rule);
+ *   all arithmetic is float64 on the integer levels, and nothing is accumulated with atomics: two calls give the same bits. */
+/* out = Q_L(in), n elements; bit-exact against its numpy statement. */
+int srhip_tensor2levels(const float* in, float* out, long n, int L, void* stream);
+/* srhip_metrics_psnr_family at L levels: Q_L on both images (skipped if inputs_are_levels: E and H hold the levels 0 .. L),
+ * border crop, then per slot out[b][slot][4] = PSNR, PSNR_Y, MSE, NRMSE in fp64 with
+ *   MSE in L-levels^2 (a sum of integers: exact below 2^53), PSNR = 20 log10(L / sqrt(max(mse, 1e-45))),
+ *   PSNR_Y the same on L * clamp((219.0 * v / L + 16) / 255, 0, 1) (the reference's Y of a grey image: 65.481 + 128.553 +
+ *   24.966 = 219), NRMSE = sqrt(mse) / den with the ymax / lo / den == 0 -> 1 rules of the 8-bit entry point in L levels;
+ *   slot 0 divides by the pixel count, a ROI slot by its count, a count of 0 by 1.
+ * workspace doubles: srhip_metrics_ws(B, nth). */
+int srhip_metrics_psnr_family_lv(const float* E, const float* Hh, int B, int H, int W, int border,
+                                 const int* thresholds_dev, int nth, int L, int inputs_are_levels, double* workspace,
+                                 double* out, void* stream);
+/* srhip_metrics_ssim at L levels: x = level / L, the same 11x11 sigma-1.5 valid window, C1 = 1e-4, C2 = 9e-4, the ROI read at
+ * the window centre (so cropped by 5), an empty ROI gives 0 / 1.  The window moments and the SSIM map are float64 (the float32
+ * sigma^2 = E[x^2] - E[x]^2 of the 8-bit entry point is 1e-3 a pixel off on bright smooth images); one (sum, count) per block
+ * goes to the workspace and a second kernel adds them in a fixed order.  out[b][slot] fp64.
+ * workspace doubles: srhip_metrics_ssim_lv_ws(B, H, W, border, nth) (0: the image is smaller than the window). */
+long srhip_metrics_ssim_lv_ws(int B, int H, int W, int border, int nth);
+int srhip_metrics_ssim_lv(const float* E, const float* Hh, int B, int H, int W, int border,
+                          const int* thresholds_dev, int nth, int L, int inputs_are_levels, double* workspace,
+                          double* out, void* stream);
+
 /* Weight (and bias) gradients of up to 40 3x3 convolutions of ONE shape -- the body of an
  * EDSR-style stack (network_nlsn.py:72-93,325-345 backward) -- in one contraction launch plus one
  * reducer launch: item k: dW_k[Cout][Cin][3][3] = sum_px dY_k (x) shifted X_k, db_k = sum_px dY_k.

@@ -15,3 +15,13 @@ static __device__ __forceinline__ float unit_of(unsigned v, unsigned in_max, dou
 static __device__ __forceinline__ unsigned level_of(float x, float out_max) {
   return (unsigned)rintf(__fmul_rn(fminf(fmaxf(x, 0.f), 1.f), out_max));
 }
+
+// A pixel of the metrics at L levels (small.hip, ssim.hip: --metric_levels): its level at L, and the 8-bit level the ROI is
+// thresholded at.  A float image is quantised by either white level directly; a level v of an image that holds levels goes
+// back through np.float32(v / L) (unit_of), so both forms of one image give one ROI.
+static __device__ __forceinline__ float metric_level(float v, int is_levels, float fL) {
+  return is_levels ? v : (float)level_of(v, fL);
+}
+static __device__ __forceinline__ float metric_level8(float v, int is_levels, unsigned L) {
+  return (float)level_of(is_levels ? unit_of((unsigned)fminf(fmaxf(v, 0.f), (float)L), L, (double)L) : v, 255.f);
+}

@@ -3,6 +3,7 @@
 // metric sweep.
 #include "common.h"
 #include "kernels.h"
+#include "levels.h"
 
 namespace {
 
@@ -299,6 +300,36 @@ __global__ void k_u8ify(const float* __restrict__ in, float* __restrict__ out, l
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
     out[i] = u8f(in[i]);
 }
+__global__ void k_levels(const float* __restrict__ in, float* __restrict__ out, long n, float fL) {  // Q_L (levels.h)
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+    out[i] = (float)level_of(in[i], fL);
+}
+// one block's accumulators -> raw[b][th][blk][8] doubles: sse, ssey, cnt, ymax, ymin_roi, ymin_all (the four waves in a fixed order)
+__device__ __forceinline__ void metrics_block_out(const MetAcc (&acc)[MAXTH], float ymin_all, double* __restrict__ raw, int b,
+                                                  int nb, int nth) {
+  __shared__ double sh[4][6];
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const double ya = wave_min_d((double)ymin_all);
+#pragma unroll
+  for (int k = 0; k < MAXTH; ++k) {
+    if (k > nth) break;                            // block-uniform
+    const double s0 = wave_sum_d(acc[k].sse), s1 = wave_sum_d(acc[k].ssey);
+    const double s2 = wave_sum_d((double)acc[k].cnt);
+    const double s3 = wave_max_d((double)acc[k].ymax), s4 = wave_min_d((double)acc[k].ymin);
+    __syncthreads();
+    if (lane == 0) { sh[wv][0] = s0; sh[wv][1] = s1; sh[wv][2] = s2; sh[wv][3] = s3; sh[wv][4] = s4; sh[wv][5] = ya; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double* o = raw + (((long)b * (nth + 1) + k) * nb + blockIdx.x) * 8;
+      o[0] = sh[0][0] + sh[1][0] + sh[2][0] + sh[3][0];
+      o[1] = sh[0][1] + sh[1][1] + sh[2][1] + sh[3][1];
+      o[2] = sh[0][2] + sh[1][2] + sh[2][2] + sh[3][2];
+      o[3] = fmax(fmax(sh[0][3], sh[1][3]), fmax(sh[2][3], sh[3][3]));
+      o[4] = fmin(fmin(sh[0][4], sh[1][4]), fmin(sh[2][4], sh[3][4]));
+      o[5] = fmin(fmin(sh[0][5], sh[1][5]), fmin(sh[2][5], sh[3][5]));
+    }
+  }
+}
 // raw[b][th][blk][8] doubles: sse, ssey, cnt, ymax, ymin_roi, ymin_all
 __global__ void __launch_bounds__(256) k_metrics_pass(const float* __restrict__ E, const float* __restrict__ Hh,
                                                       double* __restrict__ raw, int H, int W, int border,
@@ -329,32 +360,54 @@ __global__ void __launch_bounds__(256) k_metrics_pass(const float* __restrict__ 
       }
     }
   }
-  __shared__ double sh[4][6];
-  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const double ya = wave_min_d((double)ymin_all);
+  metrics_block_out(acc, ymin_all, raw, b, nb, nth);
+}
+// Y(a) - Y(t) with Y(v) = L * clamp((219 v / L + 16) / 255, 0, 1).  No contraction here: left to the compiler the difference
+// becomes fma(L, ca, -(L * ct)), which is the rounding error of L * ct -- not 0 -- where the two levels are equal.
+__device__ __forceinline__ double ycb_lv_diff(double a, double t, double L) {
+#pragma clang fp contract(off)
+  const double ya = L * fmin(fmax((219.0 * a / L + 16.0) / 255.0, 0.0), 1.0);
+  const double yt = L * fmin(fmax((219.0 * t / L + 16.0) / 255.0, 0.0), 1.0);
+  return ya - yt;
+}
+// the same pass at L levels (--metric_levels): both images quantised by Q_L, the ROI thresholded at the 8-bit level of the
+// target (levels.h), Y in double.  Differences of integer levels: sse is exact below 2^53.  raw as above.
+__global__ void __launch_bounds__(256) k_metrics_pass_lv(const float* __restrict__ E, const float* __restrict__ Hh,
+                                                         double* __restrict__ raw, int H, int W, int border,
+                                                         const int* __restrict__ ths, int nth, int L, int in_is_lv) {
+  const int b = blockIdx.y, nb = gridDim.x;
+  const int h = H - 2 * border, w = W - 2 * border;
+  const long n = (long)h * w;
+  const float fL = (float)L;
+  const double dL = (double)L;
+  MetAcc acc[MAXTH];
+  float ymin_all = 3.0e38f;
 #pragma unroll
-  for (int k = 0; k < MAXTH; ++k) {
-    if (k > nth) break;                            // block-uniform
-    const double s0 = wave_sum_d(acc[k].sse), s1 = wave_sum_d(acc[k].ssey);
-    const double s2 = wave_sum_d((double)acc[k].cnt);
-    const double s3 = wave_max_d((double)acc[k].ymax), s4 = wave_min_d((double)acc[k].ymin);
-    __syncthreads();
-    if (lane == 0) { sh[wv][0] = s0; sh[wv][1] = s1; sh[wv][2] = s2; sh[wv][3] = s3; sh[wv][4] = s4; sh[wv][5] = ya; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double* o = raw + (((long)b * (nth + 1) + k) * nb + blockIdx.x) * 8;
-      o[0] = sh[0][0] + sh[1][0] + sh[2][0] + sh[3][0];
-      o[1] = sh[0][1] + sh[1][1] + sh[2][1] + sh[3][1];
-      o[2] = sh[0][2] + sh[1][2] + sh[2][2] + sh[3][2];
-      o[3] = fmax(fmax(sh[0][3], sh[1][3]), fmax(sh[2][3], sh[3][3]));
-      o[4] = fmin(fmin(sh[0][4], sh[1][4]), fmin(sh[2][4], sh[3][4]));
-      o[5] = fmin(fmin(sh[0][5], sh[1][5]), fmin(sh[2][5], sh[3][5]));
+  for (int k = 0; k < MAXTH; ++k) { acc[k].sse = 0; acc[k].ssey = 0; acc[k].cnt = 0; acc[k].ymax = 0.f; acc[k].ymin = 3.0e38f; }
+  int thv[MAXTH];
+#pragma unroll
+  for (int k = 0; k < MAXTH; ++k) thv[k] = (k >= 1 && k <= nth) ? ths[k - 1] : 0;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += nb * 256L) {
+    const int yy = i / w + border, xx = i % w + border;
+    const long o = ((long)b * H + yy) * W + xx;
+    const float a = metric_level(E[o], in_is_lv, fL), t = metric_level(Hh[o], in_is_lv, fL);
+    const float t8 = metric_level8(Hh[o], in_is_lv, (unsigned)L);
+    const double d = (double)a - (double)t;
+    const double dyv = ycb_lv_diff((double)a, (double)t, dL);
+    ymin_all = fminf(ymin_all, t);
+#pragma unroll
+    for (int k = 0; k < MAXTH; ++k) {
+      if (k <= nth && (k == 0 || t8 >= (float)thv[k])) {
+        acc[k].sse += d * d; acc[k].ssey += dyv * dyv; acc[k].cnt += 1;
+        acc[k].ymax = fmaxf(acc[k].ymax, t); acc[k].ymin = fminf(acc[k].ymin, t);
+      }
     }
   }
+  metrics_block_out(acc, ymin_all, raw, b, nb, nth);
 }
-// out[b][th][4] doubles: psnr, psnr_y, mse, nrmse
+// out[b][th][4] doubles: psnr, psnr_y, mse, nrmse; peak: the white level (255 for the 8-bit metrics)
 __global__ void k_metrics_fin(const double* __restrict__ raw, double* __restrict__ out, int nimg_th, int nb,
-                              int nth1, long npix) {
+                              int nth1, long npix, double peak) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nimg_th) return;
   const int k = i % nth1;
@@ -375,8 +428,8 @@ __global__ void k_metrics_fin(const double* __restrict__ raw, double* __restrict
   const double mse_p = mse < 1e-45 ? 1e-45 : mse, msey_p = msey < 1e-45 ? 1e-45 : msey;
   double den = ymax - lo;
   if (den == 0) den = 1.0;
-  out[i * 4 + 0] = 20.0 * log10(255.0 / sqrt(mse_p));
-  out[i * 4 + 1] = 20.0 * log10(255.0 / sqrt(msey_p));
+  out[i * 4 + 0] = 20.0 * log10(peak / sqrt(mse_p));
+  out[i * 4 + 1] = 20.0 * log10(peak / sqrt(msey_p));
   out[i * 4 + 2] = mse;
   out[i * 4 + 3] = sqrt(mse) / den;
 }
@@ -451,8 +504,35 @@ int srhip_metrics_psnr_family(const float* E, const float* Hh, int B, int H, int
                      thresholds_dev, nth, inputs_are_u8);
   const int n = B * (nth + 1);
   hipLaunchKernelGGL(k_metrics_fin, dim3(sr_cdiv(n, 64)), dim3(64), 0, st, workspace, out, n, nb,
-                     nth + 1, (long)(H - 2 * border) * (W - 2 * border));
+                     nth + 1, (long)(H - 2 * border) * (W - 2 * border), 255.0);
   SR_LAUNCH_CHECK("metrics_psnr_family");
+  return 0;
+}
+
+int srhip_tensor2levels(const float* in, float* out, long n, int L, void* stream) {
+  SR_REQUIRE(L >= 255 && L <= 65535, "tensor2levels: the white level is 255 .. 65535 (got %d)", L);
+  if (n <= 0) return 0;
+  long g = (n + 255) / 256;
+  if (g > 2048) g = 2048;
+  hipLaunchKernelGGL(k_levels, dim3((int)g), dim3(256), 0, (hipStream_t)stream, in, out, n, (float)L);
+  SR_LAUNCH_CHECK("tensor2levels");
+  return 0;
+}
+
+int srhip_metrics_psnr_family_lv(const float* E, const float* Hh, int B, int H, int W, int border,
+                                 const int* thresholds_dev, int nth, int L, int inputs_are_levels, double* workspace,
+                                 double* out, void* stream) {
+  SR_REQUIRE(nth >= 0 && nth <= MAXTH - 1, "metrics_lv: at most %d ROI thresholds", MAXTH - 1);
+  SR_REQUIRE(B > 0 && border >= 0 && H > 2 * border && W > 2 * border, "metrics_lv: empty image after border crop");
+  SR_REQUIRE(L >= 255 && L <= 65535, "metrics_lv: the white level is 255 .. 65535 (got %d)", L);
+  hipStream_t st = (hipStream_t)stream;
+  const int nb = 64;
+  hipLaunchKernelGGL(k_metrics_pass_lv, dim3(nb, B), dim3(256), 0, st, E, Hh, workspace, H, W, border,
+                     thresholds_dev, nth, L, inputs_are_levels);
+  const int n = B * (nth + 1);
+  hipLaunchKernelGGL(k_metrics_fin, dim3(sr_cdiv(n, 64)), dim3(64), 0, st, workspace, out, n, nb,
+                     nth + 1, (long)(H - 2 * border) * (W - 2 * border), (double)L);
+  SR_LAUNCH_CHECK("metrics_psnr_family_lv");
   return 0;
 }
 

@@ -1,11 +1,13 @@
 // SSIM as a training loss (zero-padded "same" Gaussian window, value + gradient)
 // and as an evaluation metric (11x11 "valid" window, optional ROI slots).
-// HBM/LDS-bound separable Gaussian filtering; one 32x32 output tile per block.
+// HBM/LDS-bound separable Gaussian filtering; one 32x32 output tile per block
+// (32x16 for the float64 metric at L levels).
 //
 // Loss  : dlib/loss/ssim.py:23-61, dlib/loss/main.py:154-186
 // Metric: dlib/utils/utils_image.py:1010-1198
 #include "common.h"
 #include "kernels.h"
+#include "levels.h"
 
 namespace {
 
@@ -247,6 +249,109 @@ __global__ void k_ssim_metric_fin(const double* __restrict__ raw, float* __restr
   out[i] = (float)(raw[2 * i] / c);
 }
 
+// ---------------- metric at L levels (--metric_levels) --------------------------
+// The same window on x = level / L with float64 moments: sigma^2 = E[x^2] - E[x]^2 cancels seven digits on a bright smooth
+// image, which float32 does not have.  The inputs are staged as their integer levels (exact in float32), the moments are taken
+// over the levels and scaled by 1 / L and 1 / L^2 per output pixel.  One 32 x 16 output tile per block: the five double planes
+// of the horizontal pass are [26][32], 33 KB, beside 9 KB of staged levels.  Every block stores its (sum, count) of every slot;
+// k_ssim_metric_lv_fin adds a slot's tiles in a fixed order, so the result does not depend on the order the blocks ran in.
+constexpr int LTX = 32, LTY = 16, LWS = 11;                    // output tile, window
+constexpr int LIX = LTX + LWS - 1, LIY = LTY + LWS - 1;       // staged inputs
+static_assert(2 * LIY * LIX * sizeof(float) + 5 * LIY * LTX * sizeof(double) + 72 * sizeof(double) <= 48 * 1024,
+              "k_ssim_metric_lv: static LDS");
+// raw[b][slot][tile][2] doubles (sum, count)
+__global__ void __launch_bounds__(256) k_ssim_metric_lv(const float* __restrict__ E, const float* __restrict__ Hh,
+                                                        double* __restrict__ raw, int H, int W, int border,
+                                                        const int* __restrict__ ths, int nth, int L, int in_is_lv, Taps tp) {
+  __shared__ float sx[LIY * LIX], sy[LIY * LIX];
+  __shared__ double sh[5 * LIY * LTX];
+  __shared__ double red[4][MAXTH][2];
+  const int b = blockIdx.z, oy0 = blockIdx.y * LTY, ox0 = blockIdx.x * LTX;
+  const int h = H - 2 * border, w = W - 2 * border;        // cropped image
+  const int oh = h - (LWS - 1), ow = w - (LWS - 1);        // valid output
+  const long img = (long)b * H * W;
+  const int tid = threadIdx.x;
+  const float fL = (float)L;
+  for (int i = tid; i < LIY * LIX; i += 256) {
+    const int r = i / LIX, c = i - r * LIX;
+    const int y = oy0 + r, x = ox0 + c;
+    float a = 0.f, t = 0.f;
+    if (y < h && x < w) {
+      const long o = img + (long)(y + border) * W + x + border;
+      a = metric_level(E[o], in_is_lv, fL);
+      t = metric_level(Hh[o], in_is_lv, fL);
+    }
+    sx[i] = a; sy[i] = t;
+  }
+  __syncthreads();
+  for (int i = tid; i < LIY * LTX; i += 256) {
+    const int r = i / LTX, c = i - r * LTX;
+    double a0 = 0, a1 = 0, a2 = 0, a3 = 0, a4 = 0;
+    for (int k = 0; k < LWS; ++k) {
+      const double x = (double)sx[r * LIX + c + k], y = (double)sy[r * LIX + c + k], g = (double)tp.g[k];
+      a0 += g * x; a1 += g * y; a2 += g * (x * x); a3 += g * (y * y); a4 += g * (x * y);
+    }
+    sh[(0 * LIY + r) * LTX + c] = a0; sh[(1 * LIY + r) * LTX + c] = a1; sh[(2 * LIY + r) * LTX + c] = a2;
+    sh[(3 * LIY + r) * LTX + c] = a3; sh[(4 * LIY + r) * LTX + c] = a4;
+  }
+  __syncthreads();
+  const int tx = tid & 31, ty = tid >> 5;
+  const double C1 = 0.01 * 0.01, C2 = 0.03 * 0.03;
+  const double iL = 1.0 / (double)L, iL2 = iL * iL;
+  double sum[MAXTH], cnt[MAXTH];
+#pragma unroll
+  for (int k = 0; k < MAXTH; ++k) { sum[k] = 0; cnt[k] = 0; }
+#pragma unroll
+  for (int k2 = 0; k2 < LTY / 8; ++k2) {
+    const int r = ty + 8 * k2;
+    const int y = oy0 + r, x = ox0 + tx;
+    if (y < oh && x < ow) {
+      double m[5];
+#pragma unroll
+      for (int q = 0; q < 5; ++q) {
+        double a = 0;
+        for (int k = 0; k < LWS; ++k) a += (double)tp.g[k] * sh[(q * LIY + r + k) * LTX + tx];
+        m[q] = a * (q < 2 ? iL : iL2);
+      }
+      const double sxx = m[2] - m[0] * m[0], syy = m[3] - m[1] * m[1], sxy = m[4] - m[0] * m[1];
+      const double cs = (2.0 * sxy + C2) / (sxx + syy + C2);
+      const double ss = ((2.0 * m[0] * m[1] + C1) / (m[0] * m[0] + m[1] * m[1] + C1)) * cs;
+      // the ROI pixel of this output is the centre of its window, at the 8-bit level of the target there
+      const float tcen = metric_level8(Hh[img + (long)(y + 5 + border) * W + x + 5 + border], in_is_lv, (unsigned)L);
+#pragma unroll
+      for (int k = 0; k < MAXTH; ++k)
+        if (k <= nth && (k == 0 || tcen >= (float)ths[k - 1])) { sum[k] += ss; cnt[k] += 1.0; }
+    }
+  }
+  const int wv = tid >> 6;
+#pragma unroll
+  for (int k = 0; k < MAXTH; ++k) {
+    if (k <= nth) {                                // block-uniform
+      const double s = wave_sum_d(sum[k]), c = wave_sum_d(cnt[k]);
+      if ((tid & 63) == 0) { red[wv][k][0] = s; red[wv][k][1] = c; }
+    }
+  }
+  __syncthreads();
+  if (tid <= nth) {                                // slot tid: the four waves in a fixed order
+    const long tile = (long)blockIdx.y * gridDim.x + blockIdx.x, ntile = (long)gridDim.x * gridDim.y;
+    double* o = raw + (((long)b * (nth + 1) + tid) * ntile + tile) * 2;
+    o[0] = red[0][tid][0] + red[1][tid][0] + red[2][tid][0] + red[3][tid][0];
+    o[1] = red[0][tid][1] + red[1][tid][1] + red[2][tid][1] + red[3][tid][1];
+  }
+}
+// one wave per (image, slot): lane l adds tiles l, l + 64, .. in order, then the lanes are added in wave_sum_d's fixed tree
+__global__ void __launch_bounds__(64) k_ssim_metric_lv_fin(const double* __restrict__ raw, double* __restrict__ out, int ntile,
+                                                           int nth1, double npix) {
+  const int i = blockIdx.x;
+  double s = 0, c = 0;
+  for (int j = threadIdx.x; j < ntile; j += 64) {
+    s += raw[((long)i * ntile + j) * 2];
+    c += raw[((long)i * ntile + j) * 2 + 1];
+  }
+  s = wave_sum_d(s); c = wave_sum_d(c);
+  if (threadIdx.x == 0) out[i] = s / ((i % nth1 == 0) ? npix : (c == 0 ? 1.0 : c));
+}
+
 }  // namespace
 
 extern "C" {
@@ -296,6 +401,33 @@ int srhip_metrics_ssim(const float* E, const float* Hh, int B, int H, int W, int
   hipLaunchKernelGGL(k_ssim_metric_fin, dim3(sr_cdiv(n, 64)), dim3(64), 0, st, workspace, out, n, nth + 1,
                      (double)(h - 10) * (w - 10));
   SR_LAUNCH_CHECK("metrics_ssim");
+  return 0;
+}
+
+// workspace doubles: B*(nth+1)*tiles*2
+long srhip_metrics_ssim_lv_ws(int B, int H, int W, int border, int nth) {
+  const int oh = H - 2 * border - (LWS - 1), ow = W - 2 * border - (LWS - 1);
+  if (B <= 0 || nth < 0 || border < 0 || oh <= 0 || ow <= 0) return 0;
+  return 2L * B * (nth + 1) * sr_cdiv(ow, LTX) * sr_cdiv(oh, LTY);
+}
+
+int srhip_metrics_ssim_lv(const float* E, const float* Hh, int B, int H, int W, int border,
+                          const int* thresholds_dev, int nth, int L, int inputs_are_levels, double* workspace,
+                          double* out, void* stream) {
+  SR_REQUIRE(nth >= 0 && nth <= MAXTH - 1, "metrics_ssim_lv: at most %d ROI thresholds", MAXTH - 1);
+  const int h = H - 2 * border, w = W - 2 * border;
+  SR_REQUIRE(B > 0 && border >= 0 && h >= LWS && w >= LWS, "metrics_ssim_lv: image smaller than the 11x11 window");
+  SR_REQUIRE(L >= 255 && L <= 65535, "metrics_ssim_lv: the white level is 255 .. 65535 (got %d)", L);
+  hipStream_t st = (hipStream_t)stream;
+  const Taps tp = gaussian_taps(LWS, true);
+  const int oh = h - (LWS - 1), ow = w - (LWS - 1);
+  dim3 grid(sr_cdiv(ow, LTX), sr_cdiv(oh, LTY), B);
+  SR_REQUIRE(grid.y <= 65535 && B <= 65535, "metrics_ssim_lv: more than 65535 tile rows or images");
+  hipLaunchKernelGGL(k_ssim_metric_lv, grid, dim3(256), 0, st, E, Hh, workspace, H, W, border, thresholds_dev, nth, L,
+                     inputs_are_levels, tp);
+  hipLaunchKernelGGL(k_ssim_metric_lv_fin, dim3(B * (nth + 1)), dim3(64), 0, st, workspace, out, (int)(grid.x * grid.y), nth + 1,
+                     (double)oh * ow);
+  SR_LAUNCH_CHECK("metrics_ssim_lv");
   return 0;
 }
 

@@ -8,12 +8,18 @@ given as the reference builds it, ``roi = (H_img >= th).float()``; because the
 kernels take thresholds, a mask is mapped back to its threshold when it has
 that form and rejected otherwise (``sweep`` is the fast fused entry point: all
 five metrics x all thresholds in two passes over the images).
+
+``levels`` (not a reference argument; ``--metric_levels``): the number of the white level the images are quantised to,
+255 .. 65535.  255 is the reference's metric, bit for bit.  Any other value takes the float64 kernels: MSE is then in
+levels^2, PSNR is 20 log10(levels / sqrt(mse)), SSIM is on level / levels with float64 window moments, and ``inputs_are_u8``
+/ the inputs of ``mbatch_gpu_calculate_*`` mean the levels 0 .. ``levels``.  The ROI stays ``Q_255(H) >= th``, the pixel set
+of the 8-bit metrics, whatever ``levels`` is.
 """
 import torch
 
 from srhip import ops
 
-__all__ = ['tensor2uint82float', 'mbatch_gpu_calculate_psnr', 'mbatch_gpu_calculate_mse',
+__all__ = ['tensor2uint82float', 'tensor2levels', 'mbatch_gpu_calculate_psnr', 'mbatch_gpu_calculate_mse',
            'mbatch_gpu_calculate_nrmse', 'mbatch_gpu_calculate_ssim', 'sweep']
 
 
@@ -28,14 +34,23 @@ def tensor2uint82float(img):
     return ops.tensor2uint82float(img)
 
 
-def _threshold_of(roi, img2):
-    """roi == (img2 >= th) for an integer th in [0,256]?  Returns th or raises."""
+def tensor2levels(img, levels):
+    """(img.clamp(0,1)*levels).round().clamp(0,levels): tensor2uint82float at the white level ``levels``."""
+    _need_cuda(img)
+    return ops.tensor2levels(img, levels)
+
+
+def _threshold_of(roi, img2, levels=255):
+    """roi == (img2 >= th) for an integer th in [0,256]?  Returns th or raises.  img2 holds the levels 0 .. ``levels``; the
+    threshold is one of its 8-bit levels, Q_255(float32(v / levels))."""
     if roi is None:
         return None
     assert roi.ndim == 4 and roi.shape[1] == 1 and roi.shape[0] == img2.shape[0]
     on = roi > 0
     if not bool(on.any()):
         return 256                      # empty ROI: nothing reaches the threshold
+    if levels != 255:
+        img2 = ops.tensor2uint82float((img2.double() / levels).float())
     th = int(img2[on].min().item())
     if not torch.equal(on, img2 >= th):
         raise NotImplementedError("libsrhip metrics take ROIs of the form (H >= threshold) "
@@ -43,42 +58,47 @@ def _threshold_of(roi, img2):
     return th
 
 
-def sweep(E, H, border=0, thresholds=(), inputs_are_u8=False):
+def sweep(E, H, border=0, thresholds=(), inputs_are_u8=False, levels=255):
     """All metrics in two fused passes.  E, H: (B,1,h,w) in [0,1] (or already
-    u8-valued floats).  Returns dict name -> (B, 1+len(thresholds)) tensors; column 0
-    is 'no ROI', column k the ROI H_u8 >= thresholds[k-1]."""
+    u8-valued floats; with ``levels``, floats that hold the levels 0 .. levels).  Returns dict name ->
+    (B, 1+len(thresholds)) tensors; column 0 is 'no ROI', column k the ROI H_u8 >= thresholds[k-1].  ``levels`` other than
+    255: the float64 kernels at that white level (module docstring); 'ssim' is then float64."""
     _need_cuda(E)
     assert E.shape == H.shape and E.ndim == 4 and E.shape[1] == 1, "1-channel images"
     E, H = E.float().contiguous(), H.float().contiguous()
-    fam = ops.metrics_psnr_family(E, H, border, tuple(thresholds), inputs_are_u8)
-    ssim = ops.metrics_ssim(E, H, border, tuple(thresholds), inputs_are_u8)
+    if levels == 255:
+        fam = ops.metrics_psnr_family(E, H, border, tuple(thresholds), inputs_are_u8)
+        ssim = ops.metrics_ssim(E, H, border, tuple(thresholds), inputs_are_u8)
+    else:
+        fam = ops.metrics_psnr_family_lv(E, H, border, tuple(thresholds), levels, inputs_are_u8)
+        ssim = ops.metrics_ssim_lv(E, H, border, tuple(thresholds), levels, inputs_are_u8)
     return {"psnr": fam[:, :, 0], "psnr_y": fam[:, :, 1], "mse": fam[:, :, 2],
             "nrmse": fam[:, :, 3], "ssim": ssim}
 
 
-def _one(name, img1, img2, border, roi):
+def _one(name, img1, img2, border, roi, levels=255):
     _need_cuda(img1)
     assert img1.ndim == 4 and img1.shape == img2.shape
-    th = _threshold_of(roi, img2)
-    out = sweep(img1, img2, border, () if th is None else (th,), inputs_are_u8=True)[name]
+    th = _threshold_of(roi, img2, levels)
+    out = sweep(img1, img2, border, () if th is None else (th,), inputs_are_u8=True, levels=levels)[name]
     return out[:, 0 if th is None else 1].contiguous()
 
 
-def mbatch_gpu_calculate_psnr(img1, img2, border=0, roi=None):
+def mbatch_gpu_calculate_psnr(img1, img2, border=0, roi=None, levels=255):
     """utils_image.py:843-891; inputs in [0,255]; fp64 result."""
-    return _one("psnr", img1, img2, border, roi)
+    return _one("psnr", img1, img2, border, roi, levels)
 
 
-def mbatch_gpu_calculate_mse(img1, img2, border=0, roi=None):
+def mbatch_gpu_calculate_mse(img1, img2, border=0, roi=None, levels=255):
     """utils_image.py:894-934."""
-    return _one("mse", img1, img2, border, roi)
+    return _one("mse", img1, img2, border, roi, levels)
 
 
-def mbatch_gpu_calculate_nrmse(img, y, border=0, roi=None):
+def mbatch_gpu_calculate_nrmse(img, y, border=0, roi=None, levels=255):
     """utils_image.py:937-1007."""
-    return _one("nrmse", img, y, border, roi)
+    return _one("nrmse", img, y, border, roi, levels)
 
 
-def mbatch_gpu_calculate_ssim(x, y, border=0, roi=None):
+def mbatch_gpu_calculate_ssim(x, y, border=0, roi=None, levels=255):
     """utils_image.py:1120-1198; fp32 result."""
-    return _one("ssim", x, y, border, roi)
+    return _one("ssim", x, y, border, roi, levels)

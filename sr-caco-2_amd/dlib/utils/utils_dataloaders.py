@@ -152,6 +152,15 @@ def check_in_max(in_max):
     return int(in_max)
 
 
+def check_metric_levels(levels):
+    """--metric_levels: the white level the metrics quantise both images to, 255 .. 65535 (None: 255, the reference's metrics)"""
+    if levels is None:
+        return 255
+    if isinstance(levels, bool) or int(levels) != levels or not 255 <= levels <= 65535:
+        raise ValueError(f'--metric_levels {levels}: the white level of the metrics is an integer in 255 .. 65535')
+    return int(levels)
+
+
 def refuse_16bit(args, tile):
     """what a set with a 16-bit tile cannot do, by name: raised when the set is built, before any training step"""
     if getattr(args, 'ppiw', False):

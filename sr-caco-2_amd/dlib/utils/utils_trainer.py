@@ -173,6 +173,9 @@ def fast_eval(model, data_loader, ds_name: str, split: str, tracker: dict, roi_t
         reset_tracker_eval(roi_tracker, split, ds_name)
     model.set_eval_mode()
     border = args.scale
+    from dlib.utils.utils_dataloaders import check_metric_levels
+    # --metric_levels: the sweep at another white level; not given, today's call
+    full_depth = {} if check_metric_levels(getattr(args, 'metric_levels', None)) == 255 else {'levels': int(args.metric_levels)}
     with_roi = bool(args.eval_over_roi_also)
     ths = tuple(int(t) for t in args.eval_over_roi_also_ths) if with_roi else ()
     if with_roi:
@@ -191,7 +194,7 @@ def fast_eval(model, data_loader, ds_name: str, split: str, tracker: dict, roi_t
             model = _forward_with_padding(test_data, model, args)
         vis = model.current_visuals()
         with torch.no_grad():
-            sw = metrics.sweep(vis['E'], vis['H'], border=border, thresholds=ths)
+            sw = metrics.sweep(vis['E'], vis['H'], border=border, thresholds=ths, **full_depth)
         host = {m: sw[m].double().cpu() for m in _MTRS}            # (B, 1 + nth)
         for m in _MTRS:
             _check_finite_nonneg(host[m], m)

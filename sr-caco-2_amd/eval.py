@@ -4,6 +4,7 @@
 
     python eval.py --cudaid 0 --exp_path <folder> [--data_root <datasets>] [--splits_root <folds>]
                    [--test_mode {0..4} [--test_refield 32] [--test_min_size 256]] [--in_max N]
+                   [--metric_levels N]
 
 <folder> is a reference-format experiment directory: ``config_model.yml`` (the yaml dump of the
 run's args, utils_parser.py:1397-1401) and ``best-models/G-model.pth`` (raw ``state_dict``,
@@ -53,9 +54,15 @@ def load_args(argv=None):
     ap.add_argument("--in_max", type=int, default=None,
                     help="white level of 16-bit tiles, 1 .. 65535 (default: the one the run recorded in config_model.yml, "
                          "else 65535); no effect on 8-bit tiles")
+    ap.add_argument("--metric_levels", type=int, default=None,
+                    help="white level the metrics quantise prediction and target to, 255 .. 65535 (default: the one the run "
+                         "recorded in config_model.yml, else 255: the reference's 8-bit-level metrics); the bicubic baseline "
+                         "row is measured at the same level")
     ns = ap.parse_args(argv)
     if ns.in_max is not None and not 1 <= ns.in_max <= 65535:
         ap.error(f"--in_max {ns.in_max}: the white level of 16-bit tiles is an integer in 1 .. 65535")
+    if ns.metric_levels is not None and not 255 <= ns.metric_levels <= 65535:
+        ap.error(f"--metric_levels {ns.metric_levels}: the white level of the metrics is an integer in 255 .. 65535")
     exp_path = ns.exp_path
     assert exp_path and isdir(exp_path), exp_path
     with open(join(exp_path, 'config_model.yml'), 'r') as fy:
@@ -63,6 +70,8 @@ def load_args(argv=None):
     args.distributed = False
     if ns.in_max is not None:
         args.in_max = ns.in_max
+    if ns.metric_levels is not None:
+        args.metric_levels = ns.metric_levels
     if ns.data_root is None:
         raise SystemExit("eval.py: give --data_root (or SRHIP_DATA_ROOT): the parent of the dataset folders")
     args.data_root = ns.data_root

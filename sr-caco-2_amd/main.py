@@ -180,6 +180,11 @@ def parse_input(argv=None):
     # given, 4095 for 12-bit data in a 16-bit container; no effect on 8-bit tiles.  A key of the configuration -- and of
     # config_model.yml, where eval.py and predict.py find it -- only when given.
     ap.add_argument('--in_max', type=int, default=None)
+    # (not a reference option) the white level the evaluation metrics quantise prediction and target to, 255 .. 65535 --
+    # normally the set's in_max.  Not given: 255, the reference's 8-bit-level metrics.  Given: MSE in levels^2, PSNR against
+    # that white level, SSIM in float64 (dlib.metrics.sweep); the ROIs stay defined at the 8-bit levels.  A key of the
+    # configuration and of config_model.yml -- where eval.py finds it, and a resumed run checks it -- only when given.
+    ap.add_argument('--metric_levels', type=int, default=None)
     ap.add_argument('--init_pretrained_path', type=str, default=None)        # netG['init_pretrained_path'] (utils_config.py:146)
     for k, t in IGNORED_FLAGS.items():
         if k not in cfg['train']:
@@ -238,6 +243,8 @@ def parse_input(argv=None):
                      f"(only the reference's default {dflt!r} is accepted)")
     if ns.in_max is not None and not 1 <= ns.in_max <= 65535:
         ap.error(f"--in_max {ns.in_max}: the white level of 16-bit tiles is an integer in 1 .. 65535")
+    if ns.metric_levels is not None and not 255 <= ns.metric_levels <= 65535:
+        ap.error(f"--metric_levels {ns.metric_levels}: the white level of the metrics is an integer in 255 .. 65535")
     # any non-None CLI value overrides the top-level / nested key (utils_parser.py:900-923)
     skip = set(IGNORED_FLAGS) | set(DEFAULT_ONLY_FLAGS) | {f'{nt}_{k}' for k in init_defaults} | {'init_pretrained_path'}
     for k, v in vars(ns).items():
@@ -295,17 +302,20 @@ def _resume_point(args):
         except Exception:                       # python-tagged values the safe loader refuses: compare the text
             old = {}
             txt = open(cfg_path).read()
-            for key in ('net_type', 'scale'):
+            for key in ('net_type', 'scale', 'metric_levels'):
                 import re
                 m = re.search(rf'^{key}:\s*(\S+)', txt, re.M)
                 if m:
                     old[key] = m.group(1)
         if 'net_type' not in old and isinstance(old.get('netG'), dict) and 'net_type' in old['netG']:
             old['net_type'] = old['netG']['net_type']           # (the reference's own files keep it under netG)
-        for key in ('net_type', 'scale'):
-            if key in old and str(old[key]) != str(getattr(args, key)):
+        # metric_levels, absent meaning 255: a tracker that mixed 8-bit and full-depth PSNRs would select a wrong best model
+        old.setdefault('metric_levels', 255)
+        asked = {'net_type': args.net_type, 'scale': args.scale, 'metric_levels': getattr(args, 'metric_levels', None) or 255}
+        for key, want in asked.items():
+            if key in old and str(old[key]) != str(want):
                 raise SystemExit(f"--outd {args.outd_backup} holds an experiment with {key} = {old[key]} (config_model.yml); this "
-                                 f"run asks for {getattr(args, key)}: give it a folder of its own (--outd)")
+                                 f"run asks for {want}: give it a folder of its own (--outd)")
     it_g, path_g = find_last_checkpoint(models, net_type='G',
                                         pretrained_path=args.netG.get('init_pretrained_path', '') or '')
     args.netG['checkpoint_path_netG'] = path_g
@@ -419,7 +429,7 @@ def main(argv=None):
     model = _forward_with_padding(batch, model, args)          # SwinIR: flipped-strip padding to the next window multiple
     vis = model.current_visuals()
     ths = tuple(args.eval_over_roi_also_ths) if args.eval_over_roi_also else ()
-    sw = metrics.sweep(vis['E'], vis['H'], border=args.scale, thresholds=ths)
+    sw = metrics.sweep(vis['E'], vis['H'], border=args.scale, thresholds=ths, levels=args.metric_levels or 255)
     if rank == 0:
         for k in (constants.PSNR_MTR, constants.PSNR_Y_MTR, constants.MSE_MTR, constants.NRMSE_MTR,
                   constants.SSIM_MTR):

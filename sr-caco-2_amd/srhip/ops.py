@@ -2117,6 +2117,51 @@ def metrics_ssim(E, Hh, border, thresholds=(), inputs_are_u8=False):
     return out
 
 
+def _levels(levels, who):
+    """the white level of the full-depth metrics: an integer in 255 .. 65535"""
+    if isinstance(levels, bool) or int(levels) != levels or not 255 <= levels <= 65535:
+        raise ValueError(f"{who}: levels {levels} is outside 255 .. 65535")
+    return int(levels)
+
+
+def tensor2levels(x, levels):
+    """Q_L(x) = round_half_even(clamp(x, 0, 1) * levels), ONE float32 product: tensor2uint82float at another white level"""
+    _chk(x)
+    x = x.float().contiguous()
+    out = torch.empty_like(x)
+    call("srhip_tensor2levels", _p(x), _p(out), x.numel(), _levels(levels, "tensor2levels"), _st())
+    return out
+
+
+def metrics_psnr_family_lv(E, Hh, border, thresholds=(), levels=65535, inputs_are_levels=False):
+    """metrics_psnr_family at ``levels`` grey levels (MSE in levels^2); the ROI thresholds stay 8-bit levels.  fp64
+    [B, 1+len(thresholds), 4] = PSNR, PSNR_Y, MSE, NRMSE."""
+    _chk(E, Hh)
+    B = E.shape[0]
+    H, W = E.shape[-2:]
+    nth = len(thresholds)
+    th = torch.tensor(list(thresholds) or [0], dtype=torch.int32, device=E.device)
+    ws = SCRATCH.get("met_ws", lib.srhip_metrics_ws(B, nth), torch.float64, E.device)
+    out = torch.empty(B, nth + 1, 4, dtype=torch.float64, device=E.device)
+    call("srhip_metrics_psnr_family_lv", _p(E), _p(Hh), B, H, W, border, _p(th), nth, _levels(levels, "metrics_psnr_family_lv"),
+         int(inputs_are_levels), _p(ws), _p(out), _st())
+    return out
+
+
+def metrics_ssim_lv(E, Hh, border, thresholds=(), levels=65535, inputs_are_levels=False):
+    """metrics_ssim at ``levels`` grey levels in float64, summed in a fixed order: fp64 [B, 1+len(thresholds)]"""
+    _chk(E, Hh)
+    B = E.shape[0]
+    H, W = E.shape[-2:]
+    nth = len(thresholds)
+    th = torch.tensor(list(thresholds) or [0], dtype=torch.int32, device=E.device)
+    ws = SCRATCH.get("ssim_lv_ws", max(lib.srhip_metrics_ssim_lv_ws(B, H, W, border, nth), 1), torch.float64, E.device)
+    out = torch.empty(B, nth + 1, dtype=torch.float64, device=E.device)
+    call("srhip_metrics_ssim_lv", _p(E), _p(Hh), B, H, W, border, _p(th), nth, _levels(levels, "metrics_ssim_lv"),
+         int(inputs_are_levels), _p(ws), _p(out), _st())
+    return out
+
+
 # ------------------------------------------------------------------ optimizers
 def adam_step(p, g, m, v, step, lr, b1=0.9, b2=0.999, eps=1e-8, wd=0.0, gscale=1.0, skip_flag=None):
     _chk(p, g, m, v, skip_flag)
