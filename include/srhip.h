@@ -328,6 +328,26 @@ int srhip_mlp_bwd_front_chain_f16x2(const float* X0, long ld0, int K0, const voi
                                     const float* x, long ldx, const float* stats, float* dx, long lddx, int M, int C,
                                     int hidden, const float* rowscale, int rows_per_scale, const void* W3h, float* out3,
                                     long ld3, const float* rowscale3, void* stream);
+/* The saved form of the same two kernels: the forward hands the backward what it needs, so the backward runs no GELU.
+ *   srhip_mlp_fwd_save_f16x2: srhip_mlp_fwd_f16x2 that also writes gate = Phi(h) + h phi(h) (= gelu'(h)) and
+ *     gh = gelu(h), the value it feeds to its second product (both [M][ldh]; either may be NULL, not both; h may be
+ *     NULL).  gate leaves in the activation phase, where h does; gh leaves from the accumulators during the second
+ *     product.  out and stats_out are srhip_mlp_fwd_f16x2's bits.
+ *   srhip_mlp_bwd_gate_f16x2: the backward on that gate: dh = (s * dy . W2) * gate, dx as srhip_mlp_bwd_f16x2; no
+ *     gelu(h) is written (the fc2 weight gradient takes the forward's gh, b_mode 0).  One entry point for the three
+ *     launch forms: W0h NULL = no front product (X0, K0, x0, stats0, res0 unused; dy is read), W3h NULL = no chained
+ *     product; with both it is srhip_mlp_bwd_front_chain_f16x2 with the gate in place of h.
+ * f32-accurate matmul mode only. */
+int srhip_mlp_fwd_save_f16x2(const float* x, long ldx, const float* stats, const void* W1h, const float* b1,
+                             const void* W2h, const float* b2, float* h, float* gate, float* gh, long ldh, float* out,
+                             long ldo, int M, int C, int hidden, const float* rowscale, int rows_per_scale,
+                             float* stats_out, void* stream);
+int srhip_mlp_bwd_gate_f16x2(const float* X0, long ld0, int K0, const void* W0h, const float* x0, long ldx0,
+                             const float* stats0, const float* res0, long ldres0, float* dy, long lddy,
+                             const void* W2Th, const void* W1Th, const float* gate, long ldh, float* dh,
+                             const float* x, long ldx, const float* stats, float* dx, long lddx, int M, int C,
+                             int hidden, const float* rowscale, int rows_per_scale, const void* W3h, float* out3,
+                             long ld3, const float* rowscale3, void* stream);
 /* The W-MSA half of a Swin block, forward, in one kernel (wmsa_f16.hip): one thread block per 8x8 window computes
  *   qkv = LN(x) . Wqkv^T + bqkv  (stats[T][2] = {mean, rstd} of x; Wqkv gamma-folded, bqkv beta-folded),
  *   att = softmax(q k^T / sqrt(D) + bias + shift mask) v  per head (cyclic shift 0 or 4, as srhip_window_attention_fwd_f16x2),

@@ -255,6 +255,56 @@ int srhip_mlp_bwd_front_chain_f16x2(const float* X0, long ld0, int K0, const voi
   return sr_mlp_f16(p, 1, (hipStream_t)stream);
 }
 
+int srhip_mlp_fwd_save_f16x2(const float* x, long ldx, const float* stats, const void* W1h, const float* b1,
+                             const void* W2h, const float* b2, float* h, float* gate, float* gh, long ldh, float* out,
+                             long ldo, int M, int C, int hidden, const float* rowscale, int rows_per_scale,
+                             float* stats_out, void* stream) {
+  SR_REQUIRE(x && stats && W1h && b1 && W2h && out, "mlp_fwd_save_f16x2: null operand");
+  SR_REQUIRE(gate || gh, "mlp_fwd_save_f16x2: neither gate nor gh (srhip_mlp_fwd_f16x2 is the form without them)");
+  SR_REQUIRE(!rowscale || rows_per_scale > 0, "mlp_fwd_save_f16x2: rows_per_scale must be > 0");
+  SR_REQUIRE(ldh >= hidden, "mlp_fwd_save_f16x2: ldh = %ld < hidden = %d", ldh, hidden);
+  MlpF16Args p;
+  memset(&p, 0, sizeof(p));
+  p.X = x; p.ldx = ldx; p.ln_stats = stats;
+  p.W1 = (const unsigned short*)W1h; p.N1 = hidden; p.K1 = C; p.Kp1 = sr_kp(C);
+  p.W2 = (const unsigned short*)W2h; p.N2 = C; p.K2 = hidden; p.Kp2 = sr_kp(hidden);
+  p.b1 = b1; p.b2 = b2; p.H = h; p.Gate = gate; p.GHf = gh; p.ldh = ldh; p.out = out; p.ldo = ldo; p.R = x; p.ldr = ldx;
+  p.rowscale = rowscale; p.rows_per_scale = rows_per_scale; p.stats_out = stats_out;
+  p.M = M; p.C = C; p.hid = hidden;
+  return sr_mlp_f16(p, 0, (hipStream_t)stream);
+}
+
+int srhip_mlp_bwd_gate_f16x2(const float* X0, long ld0, int K0, const void* W0h, const float* x0, long ldx0,
+                             const float* stats0, const float* res0, long ldres0, float* dy, long lddy,
+                             const void* W2Th, const void* W1Th, const float* gate, long ldh, float* dh,
+                             const float* x, long ldx, const float* stats, float* dx, long lddx, int M, int C,
+                             int hidden, const float* rowscale, int rows_per_scale, const void* W3h, float* out3,
+                             long ld3, const float* rowscale3, void* stream) {
+  SR_REQUIRE(dy && W2Th && W1Th && gate && dh && x && stats && dx, "mlp_bwd_gate_f16x2: null operand");
+  SR_REQUIRE(!W0h || (X0 && x0 && stats0 && res0), "mlp_bwd_gate_f16x2: the front product needs X0, x0, stats0 and res0");
+  SR_REQUIRE(!W0h || (K0 > 0 && K0 % 4 == 0 && ld0 % 4 == 0 && ldx0 % 4 == 0 && ldres0 % 4 == 0),
+             "mlp_bwd_gate_f16x2: K0 and the front pitches must be multiples of 4 floats");
+  SR_REQUIRE(!W3h || (out3 && ld3 % 4 == 0 && out3 != dx), "mlp_bwd_gate_f16x2: chained product needs out3 (!= dx)");
+  SR_REQUIRE((!rowscale && !rowscale3) || rows_per_scale > 0, "mlp_bwd_gate_f16x2: rows_per_scale must be > 0");
+  SR_REQUIRE(!W0h || (dy != dx && dy != res0), "mlp_bwd_gate_f16x2: dy must not alias dx or res0");
+  SR_REQUIRE(sr_matmul_mode() == 0, "mlp_bwd_gate_f16x2: f32-accurate matmul mode only");
+  MlpF16Args p;
+  memset(&p, 0, sizeof(p));
+  p.X = dy; p.ldx = lddy;
+  p.W1 = (const unsigned short*)W2Th; p.N1 = hidden; p.K1 = C; p.Kp1 = sr_kp(C);
+  p.W2 = (const unsigned short*)W1Th; p.N2 = C; p.K2 = hidden; p.Kp2 = sr_kp(hidden);
+  p.Gate = (float*)gate; p.ldh = ldh; p.dH = dh; p.out = dx; p.ldo = lddx;
+  p.R = x; p.ldr = ldx; p.R2 = dy; p.ldr2 = lddy; p.ep_stats = stats;
+  p.rowscale = rowscale; p.rows_per_scale = rows_per_scale;
+  p.M = M; p.C = C; p.hid = hidden;
+  if (W3h) { p.W3 = (const unsigned short*)W3h; p.out3 = out3; p.ld3 = ld3; p.rowscale3 = rowscale3; }
+  if (W0h) {
+    p.W0 = (const unsigned short*)W0h; p.K0 = K0; p.Kp0 = sr_kp(K0); p.X0 = X0; p.ld0 = ld0;
+    p.x0 = x0; p.ldx0 = ldx0; p.stats0 = stats0; p.res0 = res0; p.ldres0 = ldres0; p.out0 = dy; p.ldo0 = lddy;
+  }
+  return sr_mlp_f16(p, 1, (hipStream_t)stream);
+}
+
 static int conv3x3_split(int wfmt, const float* X, long ldx, const void* Wb, const float* bias, float* Y, long ldy,
                            int B, int H, int W, int Cin, int Cout, int epi, const float* R, long ldr,
                            const float* rowscale, float alpha, void* stream, const float* in_bn_coef = nullptr,

@@ -116,6 +116,9 @@ struct MlpF16Args {
   const float* b1; const float* b2;  // forward biases (b1 beta-folded)
   float* H; long ldh;                // forward: pre-activation output (may be null) | backward: its input
   float* dH; float* GH;              // backward outputs [M][ldh]
+  // the saved form (k_mlp_f16<.., .., true>): the forward writes Gate = Phi(h) + h phi(h) and GHf = gelu(h) ([M][ldh], H
+  // optional beside them); the backward reads Gate in place of H, runs no GELU and stores no gelu(h)
+  float* Gate; float* GHf;
   float* out; long ldo;
   const float* R; long ldr;          // forward: residual (x) | backward: x of the LayerNorm
   const float* R2; long ldr2;        // backward: residual gradient (dy)

@@ -91,6 +91,8 @@ __device__ __forceinline__ float gelu_fast(float x) {
 // gelu_poly2 / gelu_fast2 (the same two functions on PAIRS of f32: v_pk_mul / v_pk_fma / v_pk_add_f32) live in common.h --
 // the grouped weight-gradient launch applies the SAME x Phi(x) to the saved pre-activations in its operand prologue, so the
 // backward no longer stores gelu(h).
+// gelu_gate2 is the ONE statement of the gate Phi(x) + x phi(x) and of gl = x Phi(x) (gelu_fast2's bits): the backward of the
+// h form evaluates it on the saved h, the forward of the saved form (SV) evaluates it once and writes both.
 __device__ __forceinline__ void gelu_gate2(sr_f32x2 x, sr_f32x2& gate, sr_f32x2& gl) {
   sr_f32x2 e1;
   const sr_f32x2 cdf = gelu_poly2(x, e1);
@@ -100,7 +102,11 @@ __device__ __forceinline__ void gelu_gate2(sr_f32x2 x, sr_f32x2& gate, sr_f32x2&
 
 // AMP (forward only; srhip_set_matmul_mode(1): inference under --amp): ONE product of the leading fp16 planes -- no lo
 // planes are staged, loaded or multiplied: a third of the matrix-core work, half of the stage-image and weight traffic
-template <bool BWD, bool AMP = false>
+//
+// SV, the saved form: the forward also writes the gate and gelu(h) (p.Gate in the activation phase, where h went; p.GHf from
+// the accumulators that still hold it, a few 16-byte stores per stage of GEMM 2 -- the HBM has nothing else to do there);
+// the backward reads the gate in place of h: dh = (s dy W2) * gate, no exp / rcp / polynomial and no gelu(h) store.
+template <bool BWD, bool AMP = false, bool SV = false>
 __global__ void __launch_bounds__(256, 2) k_mlp_f16(MlpF16Args p) {
   constexpr int NPL = AMP ? 1 : 2;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -499,10 +505,11 @@ __global__ void __launch_bounds__(256, 2) k_mlp_f16(MlpF16Args p) {
   SR_TS(3)
   // the first stages of GEMM 2's weights travel while the activation math runs (the backward's gate needs the
   // registers: it requests them behind the math, in front of the token-maximum exchange)
+  // (the saved form's forward holds the gate beside gelu(h) in the activation phase: its third set waits until after it)
   if (!BWD) {
     load_b2(0, fb0);
     load_b2(1, fb1);
-    load_b2(2, fb2);
+    if (!SV) load_b2(2, fb2);
   }
 
   // ---------------- between the GEMMs: bias + GELU (forward) / the GELU gate (backward), in registers
@@ -520,10 +527,11 @@ __global__ void __launch_bounds__(256, 2) k_mlp_f16(MlpF16Args p) {
     // backward: the pre-activations of group (half, j) travel while the two groups in front of it are processed: eight
     // 16-byte loads in flight per lane (round 4 kept four: the phase ran at the latency of six dependent HBM round trips)
     f32x4 hbuf[3][4];
+    const float* const hsrc = SV ? p.Gate : p.H;     // saved form: the forward's gate, same rows, same prefetch
     auto load_h = [&](int grp, f32x4 (&hv)[4]) {
       const int unit0 = min(192 * (grp / 3) + wave * 48 + 16 * (grp % 3) + 4 * g, p.hid - 4);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) hv[i] = *(const f32x4*)(p.H + (long)min(gm[i], p.M - 1) * p.ldh + unit0);
+      for (int i = 0; i < 4; ++i) hv[i] = *(const f32x4*)(hsrc + (long)min(gm[i], p.M - 1) * p.ldh + unit0);
     };
     if (BWD) {
       load_h(0, hbuf[0]);
@@ -552,10 +560,21 @@ __global__ void __launch_bounds__(256, 2) k_mlp_f16(MlpF16Args p) {
 #pragma unroll
               for (int e = 0; e < 4; ++e) v[e] = v[e] * (rix[i] * wi[e]) + bv[e];
               if (p.H && ok) SR_ST_STREAM((f32x4*)(p.H + (long)gm[i] * p.ldh + unit0), v);
-              {
+              if constexpr (SV) {
+                sr_f32x2 ga, gb, la, lb;
+                gelu_gate2(sr_f32x2{v[0], v[1]}, ga, la);
+                gelu_gate2(sr_f32x2{v[2], v[3]}, gb, lb);
+                if (p.Gate && ok) SR_ST_STREAM((f32x4*)(p.Gate + (long)gm[i] * p.ldh + unit0), (f32x4{ga.x, ga.y, gb.x, gb.y}));
+                v = uok ? f32x4{la.x, la.y, lb.x, lb.y} : f32x4{0.f, 0.f, 0.f, 0.f};
+              } else {
                 const sr_f32x2 g0 = gelu_fast2(sr_f32x2{v[0], v[1]}), g1 = gelu_fast2(sr_f32x2{v[2], v[3]});
                 v = uok ? f32x4{g0.x, g0.y, g1.x, g1.y} : f32x4{0.f, 0.f, 0.f, 0.f};
               }
+            } else if constexpr (SV) {
+              const f32x4 gt = hcur[i];              // the forward's gate: one multiply per unit
+#pragma unroll
+              for (int e = 0; e < 4; ++e) v[e] = uok ? v[e] * (rix[i] * wi[e] * dps[i]) * gt[e] : 0.f;
+              if (ok) SR_ST_STREAM((f32x4*)(p.dH + (long)gm[i] * p.ldh + unit0), v);
             } else {
               const f32x4 hx = hcur[i];
               f32x4 gl;
@@ -583,6 +602,8 @@ __global__ void __launch_bounds__(256, 2) k_mlp_f16(MlpF16Args p) {
   if (BWD) {
     load_b2(0, fb0);
     load_b2(1, fb1);
+    load_b2(2, fb2);
+  } else if (SV) {
     load_b2(2, fb2);
   }
   SR_TS(4)
@@ -644,12 +665,33 @@ __global__ void __launch_bounds__(256, 2) k_mlp_f16(MlpF16Args p) {
 #undef SR_TERM
     }
   };
+  // saved form, forward: gelu(h) leaves from the accumulators that still hold it, two 16-byte pieces per stage of GEMM 2
+  // (behind the stage's weight request: two stages pass before a wait reaches them).  Half 1 has a pass of its own.  Half 0
+  // has to stay in registers beside half 1 and the output accumulators: GH_EARLY of its twelve pieces go out in front of
+  // pass 0, the others in the first stages of the pass (all twelve in the pass would be 20 registers in scratch).
+  constexpr int GH_EARLY = 6;
+  auto store_gh = [&](const f32x4 (&acc)[4][3], int hh, int first, int n) {
+#pragma unroll
+    for (int pc = first; pc < first + n; ++pc) {
+      if (pc < 12) {
+        const int j = pc >> 2, i = pc & 3;
+        const int unit0 = 192 * hh + wave * 48 + 16 * j + 4 * g, gmi = m0 + 16 * i + c;
+        if (unit0 < p.hid && gmi < p.M) SR_ST_STREAM((f32x4*)(p.GHf + (long)gmi * p.ldh + unit0), acc[i][j]);
+      }
+    }
+  };
 #define SR_G2(U, FB)                                                   \
   {                                                                    \
     mma2((U) % 6, FB);                                                 \
     if ((U) + 3 < 6 * NH) load_b2((U) + 3, FB);                        \
+    if constexpr (SV && !BWD) {                                        \
+      if (p.GHf) store_gh(acc1[(U) / 6], (U) / 6, ((U) < 6 ? GH_EARLY : 0) + 2 * ((U) % 6), 2);      \
+    }                                                                  \
   }
   stage_a2(acc1[0]);
+  if constexpr (SV && !BWD) {
+    if (p.GHf) store_gh(acc1[0], 0, 0, GH_EARLY);
+  }
   SR_TS(6)
   __syncthreads();
   SR_TS(7)
@@ -1232,12 +1274,18 @@ int sr_mlp_f16(MlpF16Args& p, int bwd, hipStream_t st) {
     if (gr_on && hipFuncSetAttribute((const void*)k_mlp_gr_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, GR_LDS) != hipSuccess)
       return sr_fail(-5, "mlp_f16x2: cannot reserve %d bytes of LDS", GR_LDS);
   }
-  if (!bwd && gr_on && sr_matmul_mode() != 1 && p.hid > 192) {
+  if (!bwd && gr_on && sr_matmul_mode() != 1 && p.hid > 192 && !p.Gate && !p.GHf) {
     hipLaunchKernelGGL(k_mlp_gr_fwd, dim3(sr_cdiv(sr_cdiv(p.M, BM), 2)), dim3(GR_NT), GR_LDS, st, p);
     SR_LAUNCH_CHECK("k_mlp_gr_fwd");
     return 0;
   }
-  if (bwd) hipLaunchKernelGGL(k_mlp_f16<true>, grid, dim3(256), MLP_LDS, st, p);
+  const bool sv = p.Gate || p.GHf;
+  if (sv) {
+    SR_REQUIRE(sr_matmul_mode() == 0, "mlp_f16x2: the saved form (gate / gelu(h)) runs in the f32-accurate matmul mode only");
+    SR_REQUIRE(bwd ? (p.Gate && !p.H && !p.GH && !p.GHf) : true, "mlp_f16x2: the backward takes h or the gate, not both");
+    if (bwd) hipLaunchKernelGGL((k_mlp_f16<true, false, true>), grid, dim3(256), MLP_LDS, st, p);
+    else hipLaunchKernelGGL((k_mlp_f16<false, false, true>), grid, dim3(256), MLP_LDS, st, p);
+  } else if (bwd) hipLaunchKernelGGL(k_mlp_f16<true>, grid, dim3(256), MLP_LDS, st, p);
   else if (sr_matmul_mode() == 1) hipLaunchKernelGGL((k_mlp_f16<false, true>), grid, dim3(256), MLP_LDS, st, p);     // inference under --amp
   else hipLaunchKernelGGL(k_mlp_f16<false>, grid, dim3(256), MLP_LDS, st, p);
   SR_LAUNCH_CHECK("k_mlp_f16");

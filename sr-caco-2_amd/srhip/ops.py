@@ -770,25 +770,38 @@ def mlp_f16_fusable(C, hidden):
             and fmt1(hidden, C) and fmt1(C, hidden))
 
 
-def mlp_fwd_f16(x, stats, W1, b1, W2, b2, out, h=None, rowscale=None, rows_per_scale=1, stats_out=None):
+def mlp_fwd_f16(x, stats, W1, b1, W2, b2, out, h=None, rowscale=None, rows_per_scale=1, stats_out=None, gate=None, gh=None):
     """out = x + s * (gelu(LN(x) . W1^T + b1) . W2^T + b2) in ONE kernel on the Linear GEMMs' own operands
     (W1 = planes of W1*gamma [hidden, C], W2 = planes of W2 [C, hidden], both format 1); h (optional) receives the
-    pre-activation, stats_out the {mean, rstd} of the out rows."""
-    _chk(x, stats, b1, b2, out, h, rowscale, stats_out)
+    pre-activation, stats_out the {mean, rstd} of the out rows.
+    gate / gh (optional, the saved form srhip_mlp_fwd_save_f16x2): gate = gelu'(h) = Phi(h) + h phi(h) and gh = gelu(h),
+    what mlp_bwd_f16(gate=...) and the fc2 weight gradient read in place of h."""
+    _chk(x, stats, b1, b2, out, h, rowscale, stats_out, gate, gh)
     M, C = x.shape
     hidden = b1.shape[0]
     assert W1.fmt == 1 and W2.fmt == 1 and (W1.rows, W1.K) == (hidden, C) and (W2.rows, W2.K) == (C, hidden)
     assert out.shape == (M, C) and (h is None or h.shape == (M, hidden))
-    args = (_p(x), x.stride(0), _p(stats), _p(W1.planes), _p(b1), _p(W2.planes), _p(b2), _p(h),
-            0 if h is None else h.stride(0), _p(out), out.stride(0), M, C, hidden, _p(rowscale), rows_per_scale,
-            _p(stats_out), _st())
-    if probe.on("mlp_fused"):
-        with probe.timed(("mlp_fused", M, C, hidden, "fwd"), 4.0 * M * C * hidden,
-                         4.0 * (M * (2 * C + (hidden if h is not None else 0)) + 2 * C * hidden),
-                         kernel="k_mlp_f16<false", lb_bytes=4.0 * (M * 2 * C + 2 * C * hidden)):
-            call("srhip_mlp_fwd_f16x2", *args)
+    saved = [t for t in (h, gate, gh) if t is not None]
+    nsaved = len(saved)
+    if gate is not None or gh is not None:
+        ldh = saved[0].stride(0)
+        assert all(t.shape == (M, hidden) and t.stride(0) == ldh for t in saved)
+        name = "srhip_mlp_fwd_save_f16x2"
+        args = (_p(x), x.stride(0), _p(stats), _p(W1.planes), _p(b1), _p(W2.planes), _p(b2), _p(h), _p(gate), _p(gh),
+                ldh, _p(out), out.stride(0), M, C, hidden, _p(rowscale), rows_per_scale, _p(stats_out), _st())
     else:
-        call("srhip_mlp_fwd_f16x2", *args)
+        name = "srhip_mlp_fwd_f16x2"
+        args = (_p(x), x.stride(0), _p(stats), _p(W1.planes), _p(b1), _p(W2.planes), _p(b2), _p(h),
+                0 if h is None else h.stride(0), _p(out), out.stride(0), M, C, hidden, _p(rowscale), rows_per_scale,
+                _p(stats_out), _st())
+    if probe.on("mlp_fused"):
+        # bytes: x in, out, one [M, hidden] array per saved tensor (h, gate, gelu(h)), the weights
+        with probe.timed(("mlp_fused", M, C, hidden, "fwd" if name.endswith("fwd_f16x2") else "fwd+save"), 4.0 * M * C * hidden,
+                         4.0 * (M * (2 * C + nsaved * hidden) + 2 * C * hidden),
+                         kernel="k_mlp_f16<false", lb_bytes=4.0 * (M * 2 * C + 2 * C * hidden)):
+            call(name, *args)
+    else:
+        call(name, *args)
     return out
 
 
@@ -822,22 +835,29 @@ def wmsa_fwd_f16(x, stats, Wq, bq, Wp, bp, biasF, qkv, att, out, B, H, W, heads,
     return out
 
 
-def mlp_bwd_f16(dy, W2T, W1T, h, dh, gh, x, stats, dx, rowscale=None, rows_per_scale=1, chain=None, front=None):
+def mlp_bwd_f16(dy, W2T, W1T, h, dh, gh, x, stats, dx, rowscale=None, rows_per_scale=1, chain=None, front=None, gate=None):
     """Data gradient of mlp_fwd_f16 in ONE kernel: dh = (s * dy . W2) * gelu'(h), gh = gelu(h), dx = dy +
     LayerNorm_backward(dh . W1f; x, stats).  W2T = planes of W2^T [hidden, C], W1T = planes of (W1*gamma)^T [C, hidden].
     chain = (W3, out3, rowscale3): out3 = s3 * (dx . W3^T) behind it in the same kernel (W3 = planes [C, C], format 1:
     the data gradient of the attention's proj Linear).
     front = (X0, W0, x0, stats0, res0): dy is COMPUTED in the kernel (and written): dy = res0 + LayerNorm_backward(X0 @
-    W0^T; x0, stats0) -- the qkv Linear's data gradient of the Swin block behind this one (W0 = planes [C, K0])."""
-    _chk(dy, h, dh, gh, x, stats, dx, rowscale)
+    W0^T; x0, stats0) -- the qkv Linear's data gradient of the Swin block behind this one (W0 = planes [C, K0]).
+    gate (with h = gh = None): the saved form -- dh = (s * dy . W2) * gate on the gate mlp_fwd_f16 wrote, no GELU and no
+    gelu(h) store in the kernel (srhip_mlp_bwd_gate_f16x2, the same three launch forms)."""
+    _chk(dy, h, dh, gh, x, stats, dx, rowscale, gate)
     M, C = dy.shape
-    hidden = h.shape[1]
+    assert (gate is None) != (h is None) and (gate is None or gh is None)
+    src = h if gate is None else gate
+    hidden = src.shape[1]
     assert W2T.fmt == 1 and W1T.fmt == 1 and (W2T.rows, W2T.K) == (hidden, C) and (W1T.rows, W1T.K) == (C, hidden)
     # gh None: gelu(h) is not stored -- the fc2 weight gradient reads h with b_mode=2 (linear_wgrad_grouped)
-    assert dh.shape == h.shape and dh.stride(0) == h.stride(0)
+    assert src.shape[0] == M and dh.shape == src.shape and dh.stride(0) == src.stride(0)
     assert gh is None or (gh.shape == h.shape and gh.stride(0) == h.stride(0))
     assert x.shape == (M, C) and dx.shape == (M, C)
     args = (_p(dy), dy.stride(0), _p(W2T.planes), _p(W1T.planes), _p(h), h.stride(0), _p(dh), _p(gh), _p(x),
+            x.stride(0), _p(stats), _p(dx), dx.stride(0), M, C, hidden, _p(rowscale), rows_per_scale, _st()) \
+        if gate is None else \
+           (_p(dy), dy.stride(0), _p(W2T.planes), _p(W1T.planes), _p(gate), gate.stride(0), _p(dh), _p(x),
             x.stride(0), _p(stats), _p(dx), dx.stride(0), M, C, hidden, _p(rowscale), rows_per_scale, _st())
     name = "srhip_mlp_bwd_f16x2"
     if chain is not None:
@@ -846,21 +866,28 @@ def mlp_bwd_f16(dy, W2T, W1T, h, dh, gh, x, stats, dx, rowscale=None, rows_per_s
         assert W3.fmt == 1 and (W3.rows, W3.K) == (C, C) and out3.shape == (M, C)
         args = args[:-1] + (_p(W3.planes), _p(out3), out3.stride(0), _p(rs3), _st())
         name = "srhip_mlp_bwd_chain_f16x2"
+    elif front is not None or gate is not None:
+        args = args[:-1] + (None, None, 0, None, _st())
     if front is not None:
         X0, W0, x0, st0, res0 = front
         _chk(X0, x0, st0, res0)
         K0 = X0.shape[1]
         assert W0.fmt == 1 and (W0.rows, W0.K) == (C, K0) and X0.shape[0] == M and x0.shape == (M, C) == res0.shape
-        if chain is None:
-            args = args[:-1] + (None, None, 0, None, _st())
         args = (_p(X0), X0.stride(0), K0, _p(W0.planes), _p(x0), x0.stride(0), _p(st0), _p(res0), res0.stride(0)) + args
         name = "srhip_mlp_bwd_front_chain_f16x2"
+    elif gate is not None:
+        args = (None, 0, 0, None, None, 0, None, None, 0) + args
+    if gate is not None:            # one entry point for the three launch forms
+        name = "srhip_mlp_bwd_gate_f16x2"
     if probe.on("mlp_fused"):
-        tag = ("qkv+" if front is not None else "") + "bwd" + ("+proj" if chain is not None else "")
+        tag = ("qkv+" if front is not None else "") + "bwd" + ("+proj" if chain is not None else "") \
+            + ("" if gate is None else ":gate")
         k0 = front[0].shape[1] if front is not None else 0
+        # [M, hidden] arrays through HBM: h or the gate in, dh out, gelu(h) out in the h form that stores it
+        nhid = 2 if gate is not None else (3 if gh is not None else 2)
         with probe.timed(("mlp_fused", M, C, hidden, tag),
                          4.0 * M * C * hidden + (0 if chain is None else 2.0 * M * C * C) + 2.0 * M * C * k0,
-                         4.0 * (M * (3 * C + (3 if gh is not None else 2) * hidden + (C if chain is not None else 0)
+                         4.0 * (M * (3 * C + nhid * hidden + (C if chain is not None else 0)
                                      + (k0 + 2 * C if front else 0)) + 2 * C * hidden),
                          kernel="k_mlp_f16<true",
                          # fused bound: incoming / outgoing gradients, the block's saved input rows, weights -- not h / dh / gelu(h)

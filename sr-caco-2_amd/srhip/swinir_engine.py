@@ -67,6 +67,13 @@ class SwinIREngine(Engine):
         self.fuse_wmsa = (all(ops.wmsa_f16_fusable(self.C, b.num_heads) for b in self.blocks)
                           and os.environ.get("SRHIP_WMSA_F16", "1") != "0")
 
+    def mlp_save_gate(self):
+        """The fused MLP forward of a training step saves gate = gelu'(h) and gelu(h) instead of h (read when the forward is
+        enqueued, as SRHIP_RECOMPUTE_GH is in the backward).  SRHIP_MLP_SAVE_GATE=0: h is saved, the backward evaluates the
+        gate and stores gelu(h).  SRHIP_RECOMPUTE_GH=1 (the weight gradient recomputes gelu(h) from h) needs h: the old form."""
+        return (self.fuse_mlp_h and os.environ.get("SRHIP_MLP_SAVE_GATE", "1") != "0"
+                and os.environ.get("SRHIP_RECOMPUTE_GH", "0") != "1" and not ops.lib.srhip_get_matmul_mode())
+
     def _qkv_bias(self, blk):
         """the qkv Linear's bias, or zeros when the net was built with qkv_bias=False (network_swinir.py:104)"""
         if blk.attn.qkv.bias is not None:
@@ -374,17 +381,25 @@ class SwinIREngine(Engine):
                 st_next = None
                 if fuse and j + 1 < nblk:
                     st_next = buf(f"{(bi + 1) if save else (bi + 1) % 2}.st1", T, 2)
+                gate = ghf = None
                 if self.fuse_mlp_h:
-                    h = buf(f"{k}.h", T, hid) if save else None       # inference never reads it
+                    # training saves what the backward reads (inference nothing): the gate gelu'(h) and gelu(h), both from the
+                    # forward's registers -- the MLP backward then runs no GELU and writes no gelu(h) -- or, SRHIP_MLP_SAVE_GATE=0,
+                    # h itself (the backward evaluates the gate on it and stores gelu(h) for the fc2 weight gradient)
+                    h = None
+                    if save and self.mlp_save_gate():
+                        gate, ghf = buf(f"{k}.gate", T, hid), buf(f"{k}.ghf", T, hid)
+                    elif save:
+                        h = buf(f"{k}.h", T, hid)
                     ops.mlp_fwd_f16(x1, st2, ws[f"{bi}.w1"], D.d[f"{bi}.b1"], ws[f"{bi}.w2"], blk.mlp.fc2.bias.data,
-                                    x2, h=h, rowscale=s2, rows_per_scale=H * W, stats_out=st_next)
+                                    x2, h=h, rowscale=s2, rows_per_scale=H * W, stats_out=st_next, gate=gate, gh=ghf)
                 else:
                     h = buf(f"{k}.h", T, hid)
                     ops.gemm_nt(x1, ws[f"{bi}.w1"], D.d[f"{bi}.b1"], out=h, a_mode=1, ln_stats=st2)
                     ops.gemm_nt(h, ws[f"{bi}.w2"], blk.mlp.fc2.bias.data, out=x2, a_mode=2, epi=2,
                                 R=x1, rowscale=s2, rows_per_scale=H * W, stats_out=st_next)
                 if save:
-                    sv["blocks"].append((t, st1, qkv, a, x1, st2, h))
+                    sv["blocks"].append((t, st1, qkv, a, x1, st2, h, gate, ghf))
                 t = x2
                 st1 = st_next
                 bi += 1
@@ -642,8 +657,12 @@ class SwinIREngine(Engine):
         # grouped launch +160 us each (the GELU sits on the two B-operand staging waves of the fc2 tiles, the launch is ONE
         # round of 240 blocks and ends with its slowest block): 689 against 708 patches/s -- a loss, so it stays opt-in.
         recompute_gh = (self.fuse_mlp_h and ws.use_bx3 and ops.F16X2 and os.environ.get("SRHIP_RECOMPUTE_GH", "0") == "1")
-        ghs = [None if recompute_gh else buf(f"gh{i}", T, hid) for i in range(nset)]
-        ghs2 = [None if recompute_gh else buf(f"gh{i}.p1", T, hid) for i in range(nset)] if side_on else ghs
+        # The saved form (the default; mlp_save_gate): the forward wrote the gate and gelu(h) of every block -- no gelu(h) buffers
+        # here at all, the fc2 weight gradient reads the forward's.
+        saved_gate = all(blk_sv[7] is not None for blk_sv in sv["blocks"])
+        no_gh = recompute_gh or saved_gate
+        ghs = [None if no_gh else buf(f"gh{i}", T, hid) for i in range(nset)]
+        ghs2 = [None if no_gh else buf(f"gh{i}.p1", T, hid) for i in range(nset)] if side_on else ghs
         dxh, da = buf("dxh", T, C), buf("da", T, C)
         nrot = len(gbufs)
         bi = len(self.blocks)
@@ -688,7 +707,7 @@ class SwinIREngine(Engine):
                 dh, gh, dqkv = dhs[j % nset], ghs_l[j % nset], dqkvs[j % nset]
                 blk = layer.residual_group.blocks[j]
                 p = pre + f"residual_group.blocks.{j}."
-                t, st1, qkv, a, x1, st2, h = sv["blocks"][bi]
+                t, st1, qkv, a, x1, st2, h, gate, ghf = sv["blocks"][bi]
                 heads = blk.num_heads
                 s1 = None if dp is None else dp[2 * bi]
                 s2 = None if dp is None else dp[2 * bi + 1]
@@ -698,9 +717,11 @@ class SwinIREngine(Engine):
                 if self.fuse_mlp_h:
                     # `front`: the qkv Linear's data gradient + LayerNorm backward of the block behind this one (its
                     # result is this MLP's incoming gradient g) runs as the first phase of the same kernel
-                    ops.mlp_bwd_f16(g, ws[f"{bi}.w2T"], ws[f"{bi}.w1T"], h, dh, gh, x1, st2, g1, rowscale=s2,
-                                    rows_per_scale=H * W,
-                                    chain=(ws[f"{bi}.wpT"], da, s1) if chained else None, front=front)
+                    if gate is not None:
+                        gh = ghf         # the forward's gelu(h): operand of the fc2 weight gradient as it stands
+                    ops.mlp_bwd_f16(g, ws[f"{bi}.w2T"], ws[f"{bi}.w1T"], h, dh, None if gate is not None else gh, x1, st2, g1,
+                                    rowscale=s2, rows_per_scale=H * W,
+                                    chain=(ws[f"{bi}.wpT"], da, s1) if chained else None, front=front, gate=gate)
                     front = None
                 else:
                     ops.gemm_nt(g, ws[f"{bi}.w2T"], None, out=dh, epi=3, R=h, rowscale=s2,
