@@ -1069,6 +1069,37 @@ int srhip_leaky_relu(float* x, long n, float alpha, void* stream);
  * in a hipGraph replays with the seed of that moment.  tests/philox_ref.py restates keep() in numpy. */
 int srhip_dropout(const float* x, float* out, long n, long offset, const long long* seed, int site, unsigned int thr,
                   float scale, void* stream);
+/* The LR-only augmentations of a training item -- np_blur, np_prod_binary_noise, np_add_gaussian_noise on a random block
+ * (dlib/datasets/dataset_dpsr.py:899-905,1060-1180) -- in place on the gathered low-resolution patches x [B][1][h][w], in the
+ * reference's order and with its rules; the draws are the library's own (augment.hip; tests/lr_augment_ref.py restates all of
+ * this in numpy).  Stage s = 0 blur, 1 dot noise, 2 Gaussian noise; a stage that is off, has area 0 or draws u_apply >= prob
+ * leaves its sample alone.
+ *   Draws: Philox4x32-10 as srhip_dropout's, key (low, high 32 bits of *seed), c3 = 0.  A word w is the double
+ *   u = (w + 0.5) 2^-32; a normal is sqrt(-2 ln u1) cos(2 pi u2) in float64.
+ *   Per (sample b, stage s): counter (b, 0xFFFFFFFF, s) gives w0 .. w3, counter (b, 0xFFFFFFFE, s) gives w4 .. w7; u_apply
+ *   from w0, z from (w1, w2), u_ch from w3, u_cw from w4, u_side from w5.  ratio = z * 0.01 + area (:1062),
+ *   bh = clamp(trunc(h * ratio), 0, h), bw likewise from w (the reference takes np.int64(h * ratio) unclamped and raises in
+ *   randint when the block exceeds the patch: the clamp is the one difference, for an area near 0 or 1),
+ *   ch = min(floor(u_ch (h - bh + 1)), h - bh), cw likewise.  The blur goes inside the block iff u_side >= 0.98, else outside.
+ *   Per pixel, e = (b h + y) w + x: word e % 4 of counter (low, high 32 bits of e / 4, site).  Site 1: the pixel of the dot
+ *   stage's block is kept iff word >= round(dot_p 2^32) (P(keep) = 1 - p, no rescale) and multiplied by 0 otherwise; sites 2, 3:
+ *   u1, u2 of the normal whose gaus_std-fold is added to the pixel in float64 and rounded once to float32.
+ *   Blur: scipy.ndimage.gaussian_filter(img_hwc, sigma) with its defaults -- blur_weights (DEVICE, 2 * blur_radius + 1
+ *   doubles, blur_radius = int(4 sigma + 0.5) <= 64) = exp(-0.5 k^2 / sigma^2) normalised; border 'reflect' for any radius;
+ *   the rows axis, then the columns axis, then the channel axis of length 1 as the same weighted sum; each pass accumulates in
+ *   float64 (centre tap, then the pairs from the farthest inwards, as scipy's correlate1d) and stores float32.
+ * params is a HOST struct.  prob and area in [0, 1], 0 <= dot_p < 1, gaus_std >= 0 (of the stages that are on), else an
+ * error.  workspace: 2 * B * h * w floats, needed (with blur_weights) only when blur_on; it must not overlap x.
+ * seed is a DEVICE pointer, read when the kernels run: launches captured in a hipGraph replay with the seed of that moment.
+ * No atomics; the result depends on (*seed, params, x) alone, not on B or the launch geometry. */
+typedef struct {
+  int blur_on, dot_on, gaus_on, blur_radius;
+  double blur_prob, blur_area;
+  double dot_prob, dot_area, dot_p;
+  double gaus_prob, gaus_area, gaus_std;
+} srhip_lr_augment_params;
+int srhip_lr_augment(float* x, int B, int h, int w, const long long* seed, const srhip_lr_augment_params* params,
+                     const double* blur_weights, float* workspace, void* stream);
 /* out[0] = sum(x) (fp64 accumulation); workspace: 2048 doubles. */
 int srhip_sum(const float* x, long n, float* out, double* workspace, void* stream);
 

@@ -4,26 +4,10 @@
 // offset and sees the mask of the whole tensor.  The seed is read from device memory: a launch captured in a hipGraph
 // replays with whatever the seed tensor holds then.
 #include "common.h"
+#include "philox.h"
 #include <math.h>
 
 namespace {
-
-// Philox4x32-10 of counter (c0, c1, c2, 0) under key (k0, k1)
-__device__ __forceinline__ uint4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned k0, unsigned k1) {
-  unsigned c3 = 0u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    c0 = h1 ^ c1 ^ k0;
-    c1 = l1;
-    c2 = h0 ^ c3 ^ k1;
-    c3 = l0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return uint4{c0, c1, c2, c3};
-}
 
 // One Philox call per group of four consecutive elements; a thread walks groups q, q + stride, ...  `vec`: x and out are
 // 16-byte aligned, so a whole group is one 16-byte load and one 16-byte store.  The last group may hold 1 .. 3 elements.

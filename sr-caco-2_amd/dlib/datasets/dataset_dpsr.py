@@ -200,6 +200,42 @@ class DeviceWeightedSampler:
         return ops.origin_sample(self.table, ids, u), u
 
 
+DA_SEED_SALT = 0x6C725F6175676D74          # keeps the augmentation stream (da_gen) apart from the crop stream (gen)
+
+
+def check_da_device(args):
+    """The parameters of --da_device as ops.lr_augment takes them, ((on, prob, area, sigma), (on, prob, area, p), (on, prob,
+    area, std)); a value the kernels cannot run, of a stage that is on, is refused by the name of its option."""
+    from srhip import ops
+
+    def unit(stage):
+        for k in (f'{stage}_prob', f'{stage}_area'):
+            v = float(getattr(args, k))
+            if not 0. <= v <= 1.:
+                raise ValueError(f"--da_device: {k} = {v} lies outside [0, 1]")
+        return float(getattr(args, f'{stage}_prob')), float(getattr(args, f'{stage}_area'))
+    blur = dot = gaus = (False, 0., 0., 0.)
+    if getattr(args, 'da_blur', False):
+        sigma = float(args.da_blur_sigma)
+        if not sigma > 0.:
+            raise ValueError(f"--da_device: da_blur_sigma = {sigma} must be above 0")
+        if ops.lr_blur_radius(sigma) > ops.LR_BLUR_MAX_RADIUS:
+            raise ValueError(f"--da_device: da_blur_sigma = {sigma} gives a blur radius of {ops.lr_blur_radius(sigma)}, above "
+                             f"{ops.LR_BLUR_MAX_RADIUS}")
+        blur = (True,) + unit('da_blur') + (sigma,)
+    if getattr(args, 'da_dot_bin_noise', False):
+        p = float(args.da_dot_bin_noise_p)
+        if not 0. <= p < 1.:
+            raise ValueError(f"--da_device: da_dot_bin_noise_p = {p} lies outside [0, 1)")
+        dot = (True,) + unit('da_dot_bin_noise') + (p,)
+    if getattr(args, 'da_add_gaus_noise', False):
+        std = float(args.da_add_gaus_noise_std)
+        if not 0. <= std < math.inf:
+            raise ValueError(f"--da_device: da_add_gaus_noise_std = {std} must be a finite number >= 0")
+        gaus = (True,) + unit('da_add_gaus_noise') + (std,)
+    return blur, dot, gaus
+
+
 def EvalPairsLike(args, pairs_h, pairs_l):
     """the LR resolution logic (true tile or synthesis) is EvalPairs' (utils_dataloaders.py)"""
     from dlib.utils.utils_dataloaders import EvalPairs
@@ -237,6 +273,14 @@ class ResidentTrainSet:
       * the LR-only augmentations (--da_blur / --da_dot_bin_noise / --da_add_gaus_noise, :899-905) run on the host on
         the B low-resolution patches (a few hundred pixels each) with the reference's numpy stream, then l_to_h_img is
         resized from the augmented patch on the device and clipped (:905-906);
+      * --da_device (not a reference option): the same three augmentations in place on the gathered l_im by one
+        ops.lr_augment call (srhip_lr_augment) -- no host read, no upload, no scipy per sample.  The reference's order and
+        rules (block, probabilities, scipy's Gaussian filter), the library's draws: Philox4x32-10 under a per-batch seed, a
+        one-element int64 device tensor (the batch's 'da_seed') drawn by torch.randint from ``da_gen``, a generator of the
+        set's own seeded from (myseed, rank) and a constant of its own -- the crop stream (``gen``) does not move, so origins
+        and modes equal the un-augmented epoch's batch for batch.  The blur weights are built once at construction.  The random block is
+        clamped to the patch where the reference would raise (an area near 0 or 1).  Refused by name at construction: a
+        blur radius above 64, prob or area outside [0, 1], p outside [0, 1), a negative std or sigma, sigma 0 with the blur on;
       * 16-bit tiles (PIL mode I;16; the reference's cv2.imread(path, 0) would reduce them to 8 bits) stay resident as uint16
         and reach the batch at full depth, np.float32(min(v, in_max) / in_max) with --in_max (65535; 4095 for 12-bit data):
         srhip_patch_gather_u16, and srhip_imresize_aa_u16 for the float LR tile of an HR-only pair.  Where grey levels 0 .. 255
@@ -252,6 +296,7 @@ class ResidentTrainSet:
         from dlib.datasets import lowres
         if getattr(args, 'augment', False):
             raise NotImplementedError("ResidentTrainSet: --augment (the reference drops it too: dataset_dpsr.py:860-862 'passed')")
+        da_params = check_da_device(args) if getattr(args, 'da_device', False) else None      # before any tile is read
         self.args, self.device, self.sf = args, torch.device(device), int(args.scale)
         self.psize, self.batch = int(args.h_size), int(args.batch_size)
         self.ids_h = list(pairs_h.keys())
@@ -313,6 +358,13 @@ class ResidentTrainSet:
                 thresholds=float(getattr(args, 'sample_tr_patch_th', 0) or 0) if th_style == TH_FIX else None,
                 seed=int(args.myseed or 0) + rank, names=self.ids_h)
         self.da = any(getattr(args, f, False) for f in ('da_blur', 'da_dot_bin_noise', 'da_add_gaus_noise'))
+        self.da_device = bool(getattr(args, 'da_device', False)) and self.da
+        if self.da_device:      # the draws of ops.lr_augment: a stream of the set's own, so that the crop stream does not move
+            from srhip import ops
+            self.da_params = da_params
+            self.da_weights = ops.lr_blur_weights(da_params[0][3], self.device) if da_params[0][0] else None
+            self.da_gen = torch.Generator(device=self.device)
+            self.da_gen.manual_seed((int(args.myseed or 0) * 1000003 + rank) ^ DA_SEED_SALT)
         self.ppiw_table = None
         if getattr(args, 'ppiw', False):
             self.ppiw_table = torch.from_numpy(lowres.per_color_weights(
@@ -345,7 +397,11 @@ class ResidentTrainSet:
             modes = torch.randint(0, 8, (B,), device=self.device, generator=self.gen).cpu().tolist()
             y0, x0 = [o[0] for o in org], [o[1] for o in org]
             batch = ops.train_batch(self.hr, self.lr, ids, y0, x0, modes, P, sf, in_max=self.in_max)
-            if self.da:       # LR-only augmentations (:899-905): B patches of (P / s)^2 pixels through the reference's numpy code
+            if self.da_device:      # LR-only augmentations (:899-905) in place on the device, one seed per batch
+                batch['da_seed'] = torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64, device=self.device,
+                                                 generator=self.da_gen)       # stays on the device: the kernels read it there
+                ops.lr_augment(batch['l_im'], batch['da_seed'], self.da_params, self.da_weights)
+            elif self.da:     # LR-only augmentations (:899-905): B patches of (P / s)^2 pixels through the reference's numpy code
                 from dlib.datasets import lowres
                 host = batch['l_im'].permute(0, 2, 3, 1).cpu().numpy()
                 host = np.stack([lowres.apply_lr_augmentations(np.ascontiguousarray(host[b]), self.args) for b in range(B)])

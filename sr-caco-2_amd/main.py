@@ -92,6 +92,7 @@ def get_config(net_type):
         'da_dot_bin_noise': False, 'da_dot_bin_noise_prob': 0.5, 'da_dot_bin_noise_area': 0.3, 'da_dot_bin_noise_p': 0.5,
         'da_add_gaus_noise': False, 'da_add_gaus_noise_prob': 0.5, 'da_add_gaus_noise_area': 0.3,
         'da_add_gaus_noise_std': 0.03,
+        'da_device': False,      # (not a reference option) the da_* augmentations on the device: ops.lr_augment, own draws
         'eval_over_roi_also_ths': [4, 5, 6, 7, 8, 9, 10], 'outd': './out',
         # experiment-folder options (utils_config.py:98-126): where checkpoints / best models / images go and how
         # the best model is chosen
@@ -170,7 +171,7 @@ def parse_input(argv=None):
               'sample_tr_patch_th', 'valid_n_samples'):
         ap.add_argument(f'--{k}', type=int, default=None)
     for k in ('distributed', 'amp', 'eval_over_roi_also', 'eval_graph', 'train_graph', 'eval_over_roi_also_model_select',
-              'use_interpolated_low', 'ppiw', 'da_blur', 'da_dot_bin_noise', 'da_add_gaus_noise'):
+              'use_interpolated_low', 'ppiw', 'da_blur', 'da_dot_bin_noise', 'da_add_gaus_noise', 'da_device'):
         ap.add_argument(f'--{k}', type=str2bool, default=None)
     for k in ('inter_low_th', 'inter_low_sigma', 'ppiw_min_per_col_w', 'da_blur_prob', 'da_blur_area', 'da_blur_sigma',
               'da_dot_bin_noise_prob', 'da_dot_bin_noise_area', 'da_dot_bin_noise_p', 'da_add_gaus_noise_prob',

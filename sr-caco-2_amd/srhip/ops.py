@@ -2080,6 +2080,57 @@ def origin_sample(table, ids, uniforms):
     return out
 
 
+_LrAugmentParams = struct("srhip_lr_augment_params")
+LR_BLUR_MAX_RADIUS = 64
+
+
+def lr_blur_radius(sigma):
+    """the radius of scipy.ndimage.gaussian_filter's kernel at its default truncate = 4"""
+    return int(4.0 * float(sigma) + 0.5)
+
+
+def lr_blur_weights(sigma, device):
+    """float64 [2 r + 1] on the device: scipy's normalised Gaussian weights (scipy.ndimage._filters._gaussian_kernel1d),
+    computed on the host in numpy and uploaded -- once per set, not per batch."""
+    import numpy as np
+    sigma = float(sigma)
+    if not sigma > 0:
+        raise ValueError(f"lr_blur_weights: sigma must be above 0 (got {sigma})")
+    r = lr_blur_radius(sigma)
+    if r > LR_BLUR_MAX_RADIUS:
+        raise ValueError(f"lr_blur_weights: sigma {sigma} gives a blur radius of {r}, above {LR_BLUR_MAX_RADIUS}")
+    k = np.arange(-r, r + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * k ** 2)
+    return torch.from_numpy(phi / phi.sum()).to(device)
+
+
+def lr_augment(x, seed, params, blur_weights=None):
+    """The reference's three LR-only augmentations (np_blur, np_prod_binary_noise, np_add_gaussian_noise,
+    dataset_dpsr.py:899-905,1060-1180) in place on x, float32 [B, 1, h, w] contiguous, with the library's draws
+    (srhip_lr_augment; tests/lr_augment_ref.py is the numpy statement).  ``seed``: a one-element int64 CUDA tensor, read by the
+    kernels.  ``params``: ((on, prob, area, sigma), (on, prob, area, p), (on, prob, area, std)) for blur, dot noise, Gaussian
+    noise.  ``blur_weights``: lr_blur_weights(sigma, device), built once by the caller; None builds and uploads them here."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 1 and x.is_contiguous()):
+        raise SrhipError("lr_augment: x is a contiguous float32 CUDA/HIP tensor [B, 1, h, w]")
+    if not (seed.is_cuda and seed.dtype == torch.int64 and seed.numel() == 1):
+        raise SrhipError("lr_augment: the seed is a one-element int64 CUDA/HIP tensor")
+    (b_on, b_prob, b_area, sigma), (d_on, d_prob, d_area, d_p), (g_on, g_prob, g_area, g_std) = params
+    B, _, h, w = x.shape
+    radius, ws = 0, None
+    if b_on:
+        radius = lr_blur_radius(sigma)
+        if blur_weights is None:
+            blur_weights = lr_blur_weights(sigma, x.device)
+        if not (blur_weights.is_cuda and blur_weights.dtype == torch.float64 and blur_weights.is_contiguous()
+                and blur_weights.numel() == 2 * radius + 1):
+            raise SrhipError(f"lr_augment: blur_weights is a float64 CUDA/HIP tensor of 2 * {radius} + 1 weights")
+        ws = SCRATCH.get("lr_augment_ws", 2 * x.numel(), device=x.device)
+    p = _LrAugmentParams(int(bool(b_on)), int(bool(d_on)), int(bool(g_on)), radius, float(b_prob), float(b_area),
+                         float(d_prob), float(d_area), float(d_p), float(g_prob), float(g_area), float(g_std))
+    call("srhip_lr_augment", _p(x), B, h, w, _p(seed), ctypes.addressof(p), _p(blur_weights) if b_on else None, _p(ws), _st())
+    return x
+
+
 def train_batch(hr_tiles, lr_tiles, ids, y0, x0, modes, patch_size, sf, in_max=None):
     """The batch dict the reference's trainer feeds ModelPlain (keys l_im, h_im; dataset_dpsr.py:981-1005)
     from resident tiles: HR crop at (y0, x0), LR crop at (y0 // sf, x0 // sf) of size patch_size // sf,
