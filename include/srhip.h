@@ -1100,6 +1100,46 @@ typedef struct {
 } srhip_lr_augment_params;
 int srhip_lr_augment(float* x, int B, int h, int w, const long long* seed, const srhip_lr_augment_params* params,
                      const double* blur_weights, float* workspace, void* stream);
+/* ---- the camera model of --lr_synth psf (lr_synth.hip; not a reference option): the low-resolution image of an HR-only pair
+ * (dlib/datasets/dataset_dpsr.py:798-824, where the reference takes util.imresize_np) as a wider point spread function, larger
+ * camera pixels and photon shot noise plus read noise give it:
+ *   clean = bin_s(G_sigma * HR),  n ~ Poisson(photons * clean),  LR = float32((n + read_std * z) / photons),  z ~ N(0, 1),
+ * neither quantised nor clipped, no offset.  dlib/datasets/lowres.py restates both entry points in numpy (psf_bin_np,
+ * photon_noise_np). */
+/* clean = bin_s(G_sigma * HR).  src: B images [H][W], kind 0 float32, 1 uint8 (read as np.float32(v / 255.)), 2 uint16 (read as
+ * np.float32(min(v, in_max) / float(in_max)), 1 <= in_max <= 65535: srhip_imresize_aa_u16's rule; in_max is ignored for the
+ * other kinds); dst: B float32 images [H / s][W / s], H and W multiples of s, 2 <= s <= 16; tmp: B * H * (W / s) floats of
+ * scratch.  G_sigma is scipy.ndimage.gaussian_filter at its defaults on the HR grid (radius r = int(4 sigma + 0.5) <= 64,
+ * border 'reflect' for any radius, sigma = 0: no blur), bin_s the mean over s x s pixels.  Per axis both are ONE strided
+ * correlation with the n_taps = 2 r + s weights (DEVICE, doubles) box_s (*) gaussian,
+ *   weights[k] = (sum_{j < s, 0 <= k - j <= 2 r} g[k - j]) / s,   g = exp(-0.5 m^2 / sigma^2) normalised, m = -r .. r,
+ * built once on the host (ops.psf_bin_weights):  out[o] = sum_k weights[k] in[reflect(o s - r + k)], k ascending, accumulated in
+ * float64 and rounded once to float32.  Two launches: along the rows of the image into tmp, then down its columns into dst.
+ * Rows of W / s floats that are a multiple of 4 on 16-byte aligned buffers move as 16-byte accesses, others as scalars.  No
+ * atomics; bit-identical from run to run.  Refused: a NULL pointer, H or W no multiple of s, s outside 2 .. 16, n_taps - s odd
+ * or negative, a radius above 64, buffers that overlap. */
+int srhip_psf_bin(const void* src, int kind, int in_max, const double* weights, int n_taps, float* tmp, float* dst, int B, int H,
+                  int W, int s, void* stream);
+/* x = float32((Poisson(photons * x) + read_std * z) / photons) in place on x [B][1][h][w], for the samples b with on[b] != 0
+ * (on: a HOST array of B flags, NULL = every sample; the others keep their bits).  photons: the expected count of a pixel at
+ * white level, in (0, 1e6]; read_std >= 0 in counts (0: no normal is drawn).
+ *   Draws: Philox4x32-10 as srhip_dropout's, key (low, high 32 bits of *seed), c3 = 0.  A word w is the double
+ *   u = (w + 0.5) 2^-32; the normal is sqrt(-2 ln u1) cos(2 pi u2) in float64 (srhip_lr_augment's rules).  For pixel
+ *   i = y w + x of sample b, counter (i, b, j), j = 0 .. 7, gives (U, V) of the Poisson attempts 2 j (words 0, 1) and 2 j + 1
+ *   (words 2, 3); word 0 of counter (i, b, 0) is also the one uniform of the inversion; counter (i, b, 0x80000000) gives u1, u2
+ *   of the normal (words 0, 1).
+ *   lambda = photons * (double)x.  lambda <= 0 (or not a number): n = 0.  lambda < 30: inversion by sequential search,
+ *   p_0 = exp(-lambda), p_k = p_{k-1} * lambda / k, cumulated in float64, n = the first k with u <= p_0 + .. + p_k, at most 255.
+ *   lambda >= 30: W. Hoermann's transformed rejection PTRS (1993) with b = 0.931 + 2.53 sqrt(lambda), a = -0.059 + 0.02483 b,
+ *   1 / alpha = 1.1239 + 1.1328 / (b - 3.4), v_r = 0.9277 - 3.6224 / (b - 2): per attempt U = u - 0.5, us = 0.5 - |U|,
+ *   k = floor((2 a / us + b) U + lambda + 0.43); accept if us >= 0.07 and V <= v_r; reject if k < 0 or (us < 0.013 and V > us);
+ *   else accept iff ln V + ln(1 / alpha) - ln(a / us^2 + b) <= -lambda + k ln lambda - lgamma(k + 1).  After 16 rejections
+ *   n = rint(lambda).
+ * seed is a DEVICE pointer, read when the kernel runs: a launch captured in a hipGraph replays with the seed of that moment.
+ * One launch per 1024 samples that has a flag set.  No atomics; the result depends on (*seed, b, i, x, photons, read_std)
+ * alone, not on B or the launch geometry. */
+int srhip_photon_noise(float* x, int B, int h, int w, const long long* seed, const unsigned char* on, double photons,
+                       double read_std, void* stream);
 /* out[0] = sum(x) (fp64 accumulation); workspace: 2048 doubles. */
 int srhip_sum(const float* x, long n, float* out, double* workspace, void* stream);
 

@@ -201,6 +201,7 @@ class DeviceWeightedSampler:
 
 
 DA_SEED_SALT = 0x6C725F6175676D74          # keeps the augmentation stream (da_gen) apart from the crop stream (gen)
+LR_SYNTH_SEED_SALT = 0x70686F746F6E7321    # keeps the noise stream of --lr_synth psf (synth_gen) apart from both
 
 
 def check_da_device(args):
@@ -281,6 +282,14 @@ class ResidentTrainSet:
         and modes equal the un-augmented epoch's batch for batch.  The blur weights are built once at construction.  The random block is
         clamped to the patch where the reference would raise (an area near 0 or 1).  Refused by name at construction: a
         blur radius above 64, prob or area outside [0, 1], p outside [0, 1), a negative std or sigma, sigma 0 with the blur on;
+      * --lr_synth psf (not a reference option): the resident float tile of an HR-only pair is the camera model's clean image
+        bin_s(G_sigma * HR) (srhip_psf_bin, once per tile at construction) instead of util.imresize_np, and every batch gets fresh
+        photon and read noise, LR = (Poisson(photons * clean) + read_std * N(0, 1)) / photons, by one ops.photon_noise call
+        (srhip_photon_noise) in place on the gathered l_im of its HR-only samples -- before the da_* stages and before
+        l_to_h_img is made -- under the batch's 'lr_synth_seed', a one-element int64 device tensor drawn from ``synth_gen``, a
+        third generator seeded from (myseed, rank) and a constant of its own: ``gen`` and ``da_gen`` do not move.  photons 0: no
+        noise and no launch.  Every other pair keeps its true tile or the reference's synthesis.  Refused by name at
+        construction: a set without an HR-only pair, negative values, a blur radius above 64, read noise without photons;
       * 16-bit tiles (PIL mode I;16; the reference's cv2.imread(path, 0) would reduce them to 8 bits) stay resident as uint16
         and reach the batch at full depth, np.float32(min(v, in_max) / in_max) with --in_max (65535; 4095 for 12-bit data):
         srhip_patch_gather_u16, and srhip_imresize_aa_u16 for the float LR tile of an HR-only pair.  Where grey levels 0 .. 255
@@ -321,6 +330,10 @@ class ResidentTrainSet:
                                  f"that is not a CACO-2 tile is cropped uniformly only; first: "
                                  f"{self.ids_h[self.hr_only.index(True)]})")
         self.in_max = check_in_max(getattr(args, 'in_max', None))           # the white level of 16-bit tiles (--in_max)
+        self.lr_synth = ev.lr_synth     # None, or (sigma, photons, read_std) of --lr_synth psf: checked by EvalPairs
+        if self.lr_synth is not None and not any(self.hr_only):
+            raise ValueError("--lr_synth psf: the set has no HR-only pair (every pair has a true low-resolution tile or is a "
+                             "CACO-2 tile, whose low-resolution image the option does not touch)")
         hr_host = []
         for idx, (hk, lk) in enumerate(zip(self.ids_h, self.ids_l)):
             h_path = pairs_h[hk]['abs_path']
@@ -365,6 +378,9 @@ class ResidentTrainSet:
             self.da_weights = ops.lr_blur_weights(da_params[0][3], self.device) if da_params[0][0] else None
             self.da_gen = torch.Generator(device=self.device)
             self.da_gen.manual_seed((int(args.myseed or 0) * 1000003 + rank) ^ DA_SEED_SALT)
+        if self.lr_synth is not None:     # the noise seeds of --lr_synth psf: a third stream, so that gen and da_gen do not move
+            self.synth_gen = torch.Generator(device=self.device)
+            self.synth_gen.manual_seed((int(args.myseed or 0) * 1000003 + rank) ^ LR_SYNTH_SEED_SALT)
         self.ppiw_table = None
         if getattr(args, 'ppiw', False):
             self.ppiw_table = torch.from_numpy(lowres.per_color_weights(
@@ -397,6 +413,12 @@ class ResidentTrainSet:
             modes = torch.randint(0, 8, (B,), device=self.device, generator=self.gen).cpu().tolist()
             y0, x0 = [o[0] for o in org], [o[1] for o in org]
             batch = ops.train_batch(self.hr, self.lr, ids, y0, x0, modes, P, sf, in_max=self.in_max)
+            if self.lr_synth is not None:     # --lr_synth psf: fresh photon and read noise on the HR-only samples' clean patches
+                batch['lr_synth_seed'] = torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64, device=self.device,
+                                                       generator=self.synth_gen)   # stays on the device: the kernel reads it there
+                on = [self.hr_only[i] for i in ids]
+                if self.lr_synth[1] > 0. and any(on):
+                    ops.photon_noise(batch['l_im'], batch['lr_synth_seed'], self.lr_synth[1], self.lr_synth[2], on)
             if self.da_device:      # LR-only augmentations (:899-905) in place on the device, one seed per batch
                 batch['da_seed'] = torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64, device=self.device,
                                                  generator=self.da_gen)       # stays on the device: the kernels read it there

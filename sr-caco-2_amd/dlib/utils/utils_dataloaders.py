@@ -161,6 +161,42 @@ def check_metric_levels(levels):
     return int(levels)
 
 
+LR_SYNTHS = ('bicubic', 'psf')
+LR_SYNTH_EVAL_SALT = 0x6C725F73796E7468        # + item index: the noise seed of a validation / test item under --lr_synth psf
+
+
+def check_lr_synth(args):
+    """--lr_synth (not a reference option): None for 'bicubic' (or no key: util.imresize_np, the reference's LR image of an
+    HR-only pair), else (sigma, photons, read_std) of the camera model 'psf' -- clean = bin_s(G_sigma * HR), LR = (Poisson(photons
+    * clean) + read_std * N(0, 1)) / photons; photons 0: no noise.  A value the kernels cannot run is refused by option name."""
+    from dlib.datasets import lowres
+    kind = getattr(args, 'lr_synth', None)
+    if kind is None:
+        kind = 'bicubic'
+    if kind not in LR_SYNTHS:
+        raise ValueError(f"--lr_synth {kind}: one of {', '.join(LR_SYNTHS)}")
+    vals = {}
+    for k in ('lr_synth_psf_sigma', 'lr_synth_photons', 'lr_synth_read_std'):
+        v = getattr(args, k, None)
+        v = 0. if v is None else v
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0. <= v < math.inf:
+            raise ValueError(f"--{k} {v}: a finite number >= 0")
+        vals[k] = float(v)
+    sigma, photons, read_std = vals['lr_synth_psf_sigma'], vals['lr_synth_photons'], vals['lr_synth_read_std']
+    if kind != 'psf':
+        if sigma or photons or read_std:
+            raise ValueError("--lr_synth_psf_sigma / --lr_synth_photons / --lr_synth_read_std need --lr_synth psf")
+        return None
+    if int(4.0 * sigma + 0.5) > lowres.LR_BLUR_MAX_RADIUS:
+        raise ValueError(f"--lr_synth_psf_sigma {sigma} gives a blur radius of {int(4.0 * sigma + 0.5)}, above "
+                         f"{lowres.LR_BLUR_MAX_RADIUS}")
+    if photons > lowres.LR_SYNTH_MAX_PHOTONS:
+        raise ValueError(f"--lr_synth_photons {photons}: at most {lowres.LR_SYNTH_MAX_PHOTONS:g}")
+    if read_std > 0. and photons == 0.:
+        raise ValueError(f"--lr_synth_read_std {read_std} needs --lr_synth_photons above 0: the read noise is in photon counts")
+    return sigma, photons, read_std
+
+
 def refuse_16bit(args, tile):
     """what a set with a 16-bit tile cannot do, by name: raised when the set is built, before any training step"""
     if getattr(args, 'ppiw', False):
@@ -211,6 +247,8 @@ class EvalPairs:
         self.im_h_ids = list(pairs_h.keys())
         self.sf = args.scale
         self.in_max = check_in_max(getattr(args, 'in_max', None))       # the white level of 16-bit tiles (--in_max)
+        self.lr_synth = check_lr_synth(args)        # None: bicubic; (sigma, photons, read_std): the camera model (--lr_synth psf)
+        self._psf_weights = None
         # ids <-> floats (dataset_dpsr.py:583-590): per-image details travel through all_gather as floats
         self.im_h_ids_to_float = {k: float(i) for i, k in enumerate(self.im_h_ids)}
         self.float_to_im_h_ids = {v: k for k, v in self.im_h_ids_to_float.items()}
@@ -232,12 +270,37 @@ class EvalPairs:
         h_path = self.pairs_h[self.im_h_ids[index]]['abs_path']
         return self._true_low_path(index) is None and not lowres.is_caco2(h_path)
 
-    def low_res_f32(self, img_h: np.ndarray, device=None):
+    def low_res_f32(self, img_h: np.ndarray, device=None, index=None):
         """util.imresize_np(uint2single(img_h), 1 / sf, True) of a MOD-CROPPED HR tile (uint8 or uint16 HxWx1; a 16-bit tile is
         read by --in_max, unit_of_levels), float32 and neither quantised nor clipped: a [h, w] tensor on ``device`` from
         srhip_imresize_aa / srhip_imresize_aa_u16, or -- device None -- an hxwx1 numpy array from the host function (the path
-        of a machine without a GPU)."""
+        of a machine without a GPU).
+
+        With --lr_synth psf it is the camera model's image instead, as float32 and as unclipped: the clean tile bin_s(G_sigma *
+        HR) (srhip_psf_bin; lowres.psf_bin_np on the host) and -- for a validation / test item, ``index`` given, photons above
+        0 -- its photon and read noise applied ONCE to the whole tile as a batch of one under the seed LR_SYNTH_EVAL_SALT +
+        index (srhip_photon_noise; lowres.photon_noise_np), so every construction and eval.py later see the same LR image.
+        The training set asks for the clean tile (no index) and draws fresh noise per batch."""
         assert img_h.dtype in (np.uint8, np.uint16) and img_h.ndim == 3 and img_h.shape[2] == 1, (img_h.dtype, img_h.shape)
+        if self.lr_synth is not None:
+            sigma, photons, read_std = self.lr_synth
+            noisy = index is not None and photons > 0.
+            seed = LR_SYNTH_EVAL_SALT + int(index or 0)
+            if device is None:
+                from dlib.datasets import lowres
+                lo = lowres.psf_bin_np(np.ascontiguousarray(img_h[:, :, 0]), sigma, self.sf, self.in_max)
+                if noisy:
+                    lo = lowres.photon_noise_np(lo[None, None], seed, photons, read_std)[0][0, 0]
+                return lo[:, :, None]
+            import torch
+            from srhip import ops
+            if self._psf_weights is None or self._psf_weights.device != torch.device(device):
+                self._psf_weights = ops.psf_bin_weights(sigma, self.sf, device)
+            tile = torch.from_numpy(np.array(img_h[:, :, 0], copy=True))[None].to(device)
+            lo = ops.psf_bin(tile, self._psf_weights, self.sf, in_max=self.in_max)
+            if noisy:
+                ops.photon_noise(lo[None], torch.tensor([seed], dtype=torch.int64).to(device), photons, read_std)
+            return lo[0]
         if device is None:
             from dlib.utils.utils_image import imresize_np
             return imresize_np(unit_of_levels(img_h, self.in_max), 1 / self.sf, True)
@@ -282,14 +345,14 @@ class EvalPairs:
         deep = img_h.dtype == np.uint16       # the float32 images keep the levels of a 16-bit pair: no uint8 LR image exists
         if self.is_hr_only(index):                   # imresize_np of the mod-cropped tile, kept in float32 (:777,810-813)
             if gpu:
-                l_dev = self.low_res_f32(img_h, 'cuda')
+                l_dev = self.low_res_f32(img_h, 'cuda', index)
                 l_t = l_dev[None].cpu()
                 cmax = getattr(self.args, 'color_max', None)
                 cmax = 255. if cmax is None else float(cmax)
                 if not deep:
                     lu8 = (l_dev * cmax).clamp_(0., 255.).to(torch.uint8)[None]     # (img_l * color_max).astype(np.uint8) (:817)
             else:
-                l_t = torch.from_numpy(self.low_res_f32(img_h)).permute(2, 0, 1).contiguous()
+                l_t = torch.from_numpy(self.low_res_f32(img_h, None, index)).permute(2, 0, 1).contiguous()
             l_path = h_path
         else:
             img_l, l_path = self.low_res_u8(index, img_h_full, h_path)  # the synthesis sees the un-cropped tile (:752-760)

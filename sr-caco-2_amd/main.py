@@ -186,6 +186,14 @@ def parse_input(argv=None):
     # that white level, SSIM in float64 (dlib.metrics.sweep); the ROIs stay defined at the 8-bit levels.  A key of the
     # configuration and of config_model.yml -- where eval.py finds it, and a resumed run checks it -- only when given.
     ap.add_argument('--metric_levels', type=int, default=None)
+    # (not a reference option) how the LR image of an HR-only pair is made: 'bicubic' (default: util.imresize_np, the
+    # reference's) or 'psf', a camera model -- clean = bin_s(G_sigma * HR) with sigma in HR pixels, then per training batch
+    # LR = (Poisson(photons * clean) + read_std * N(0, 1)) / photons with photons the expected count at white level and read_std
+    # in counts; photons 0: no noise.  float32, no offset, no clipping, no quantisation.  Keys of the configuration and of
+    # config_model.yml -- where eval.py finds them -- only when --lr_synth is given.
+    ap.add_argument('--lr_synth', type=str, default=None)
+    for k in ('lr_synth_psf_sigma', 'lr_synth_photons', 'lr_synth_read_std'):
+        ap.add_argument(f'--{k}', type=float, default=None)
     ap.add_argument('--init_pretrained_path', type=str, default=None)        # netG['init_pretrained_path'] (utils_config.py:146)
     for k, t in IGNORED_FLAGS.items():
         if k not in cfg['train']:
@@ -246,6 +254,20 @@ def parse_input(argv=None):
         ap.error(f"--in_max {ns.in_max}: the white level of 16-bit tiles is an integer in 1 .. 65535")
     if ns.metric_levels is not None and not 255 <= ns.metric_levels <= 65535:
         ap.error(f"--metric_levels {ns.metric_levels}: the white level of the metrics is an integer in 255 .. 65535")
+    synth_keys = ('lr_synth_psf_sigma', 'lr_synth_photons', 'lr_synth_read_std')
+    if ns.lr_synth is None:
+        given = [k for k in synth_keys if getattr(ns, k) is not None]
+        if given:
+            ap.error(f"--{given[0]} needs --lr_synth psf")
+    else:
+        from dlib.utils.utils_dataloaders import check_lr_synth
+        for k in synth_keys:
+            if getattr(ns, k) is None:
+                setattr(ns, k, 0.)
+        try:
+            check_lr_synth(ns)
+        except ValueError as e:
+            ap.error(str(e))
     # any non-None CLI value overrides the top-level / nested key (utils_parser.py:900-923)
     skip = set(IGNORED_FLAGS) | set(DEFAULT_ONLY_FLAGS) | {f'{nt}_{k}' for k in init_defaults} | {'init_pretrained_path'}
     for k, v in vars(ns).items():

@@ -2131,6 +2131,104 @@ def lr_augment(x, seed, params, blur_weights=None):
     return x
 
 
+LR_SYNTH_MAX_PHOTONS = 1e6
+
+
+def psf_bin_weights(sigma, s, device="cuda"):
+    """float64 [2 r + s] on the device, r = lr_blur_radius(sigma): box_s (*) gaussian, the weights of srhip_psf_bin -- scipy's
+    normalised Gaussian weights (sigma = 0: the single weight 1) summed over the s pixels of a bin and divided by s.  Computed
+    on the host in numpy and uploaded -- once per set, not per tile."""
+    import math
+    import numpy as np
+    try:
+        sigma, s = float(sigma), int(s)
+    except (TypeError, ValueError):
+        raise SrhipError(f"psf_bin_weights: sigma is a number and s an integer (got {sigma!r}, {s!r})")
+    if not 0.0 <= sigma < math.inf:
+        raise SrhipError(f"psf_bin_weights: sigma must be a finite number >= 0 (got {sigma})")
+    if not 2 <= s <= 16:
+        raise SrhipError(f"psf_bin_weights: the bin side s is 2 .. 16 (got {s})")
+    r = lr_blur_radius(sigma)
+    if r > LR_BLUR_MAX_RADIUS:
+        raise SrhipError(f"psf_bin_weights: sigma {sigma} gives a blur radius of {r}, above {LR_BLUR_MAX_RADIUS}")
+    g = np.ones(1)
+    if r > 0:
+        k = np.arange(-r, r + 1)
+        phi = np.exp(-0.5 / (sigma * sigma) * k ** 2)
+        g = phi / phi.sum()
+    w = np.zeros(2 * r + s, dtype=np.float64)
+    for j in range(s):
+        w[j:j + 2 * r + 1] += g
+    return torch.from_numpy(w / float(s)).to(device)
+
+
+def psf_bin(src, weights, s, out=None, in_max=None):
+    """clean = bin_s(G_sigma * src) on a batch of 1-channel images [B, H, W], uint8 (read as v / 255), uint16 (read as
+    min(v, in_max) / in_max; in_max None = 65535) or float32 -> float32 [B, H / s, W / s]: scipy's Gaussian filter ('reflect'
+    border) and the mean over s x s pixels as one strided correlation per axis with ``weights`` = psf_bin_weights(sigma, s)
+    (srhip_psf_bin, lr_synth.hip; dlib.datasets.lowres.psf_bin_np is the numpy statement).  The clean low-resolution image of an
+    HR-only pair under --lr_synth psf."""
+    if not (torch.is_tensor(src) and src.is_cuda):
+        raise SrhipError("srhip ops need CUDA/HIP tensors (no CPU fallback exists)")
+    kinds = {torch.float32: 0, torch.uint8: 1, torch.uint16: 2}
+    if not (src.dim() == 3 and src.is_contiguous() and src.dtype in kinds and src.numel() > 0):
+        raise SrhipError(f"psf_bin: src is a contiguous uint8 / uint16 / float32 tensor [B, H, W] (got {tuple(src.shape)}, {src.dtype})")
+    if isinstance(s, bool) or int(s) != s or not 2 <= s <= 16:
+        raise SrhipError(f"psf_bin: the bin side s is 2 .. 16 (got {s})")
+    s = int(s)
+    B, H, W = src.shape
+    if H % s or W % s:
+        raise SrhipError(f"psf_bin: H and W are multiples of s (got {H} x {W}, s = {s})")
+    if not (torch.is_tensor(weights) and weights.is_cuda and weights.dtype == torch.float64 and weights.is_contiguous()
+            and weights.dim() == 1 and weights.numel() >= s and (weights.numel() - s) % 2 == 0):
+        raise SrhipError(f"psf_bin: weights is a float64 CUDA/HIP tensor of 2 * radius + {s} weights (psf_bin_weights)")
+    if (weights.numel() - s) // 2 > LR_BLUR_MAX_RADIUS:
+        raise SrhipError(f"psf_bin: a blur radius of {(weights.numel() - s) // 2}, above {LR_BLUR_MAX_RADIUS}")
+    if out is None:
+        out = torch.empty(B, H // s, W // s, device=src.device, dtype=torch.float32)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, H // s, W // s)):
+        raise SrhipError(f"psf_bin: out is a contiguous float32 CUDA/HIP tensor [{B}, {H // s}, {W // s}]")
+    tmp = SCRATCH.get("psf_bin_rows", B * H * (W // s), torch.float32, src.device)
+    try:
+        im = _in_max(in_max, "psf_bin") if src.dtype == torch.uint16 else 0
+    except ValueError as e:
+        raise SrhipError(str(e))
+    call("srhip_psf_bin", _p(src), kinds[src.dtype], im, _p(weights), weights.numel(), _p(tmp), _p(out), B, H, W, s, _st())
+    return out
+
+
+def photon_noise(x, seed, photons, read_std=0.0, on=None):
+    """x = float32((Poisson(photons * x) + read_std * z) / photons), z ~ N(0, 1), in place on x, float32 [B, 1, h, w] contiguous
+    (srhip_photon_noise, lr_synth.hip; dlib.datasets.lowres.photon_noise_np is the numpy statement): photon shot noise at
+    ``photons`` expected counts per pixel at white level plus read noise of ``read_std`` counts.  ``seed``: a one-element int64
+    CUDA tensor, read by the kernel when it runs.  ``on``: B flags, the samples to touch (None: all) -- a batch may mix HR-only
+    samples with others.  The caller does not call this for photons == 0 (no noise)."""
+    import math
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 1
+            and x.is_contiguous() and x.numel() > 0):
+        raise SrhipError("photon_noise: x is a contiguous float32 CUDA/HIP tensor [B, 1, h, w]")
+    if not (torch.is_tensor(seed) and seed.is_cuda and seed.dtype == torch.int64 and seed.numel() == 1):
+        raise SrhipError("photon_noise: the seed is a one-element int64 CUDA/HIP tensor")
+    try:
+        photons, read_std = float(photons), float(read_std)
+    except (TypeError, ValueError):
+        raise SrhipError(f"photon_noise: photons and read_std are numbers (got {photons!r}, {read_std!r})")
+    if not 0.0 < photons <= LR_SYNTH_MAX_PHOTONS:
+        raise SrhipError(f"photon_noise: photons lies in (0, 1e6] (got {photons})")
+    if not 0.0 <= read_std < math.inf:
+        raise SrhipError(f"photon_noise: read_std is a finite number >= 0 (got {read_std})")
+    B, _, h, w = x.shape
+    flags = None
+    if on is not None:
+        on = [bool(v) for v in on]
+        if len(on) != B:
+            raise SrhipError(f"photon_noise: on has one flag per sample ({B}; got {len(on)})")
+        flags = (ctypes.c_ubyte * B)(*on)
+    call("srhip_photon_noise", _p(x), B, h, w, _p(seed), None if flags is None else ctypes.addressof(flags), photons, read_std,
+         _st())
+    return x
+
+
 def train_batch(hr_tiles, lr_tiles, ids, y0, x0, modes, patch_size, sf, in_max=None):
     """The batch dict the reference's trainer feeds ModelPlain (keys l_im, h_im; dataset_dpsr.py:981-1005)
     from resident tiles: HR crop at (y0, x0), LR crop at (y0 // sf, x0 // sf) of size patch_size // sf,
