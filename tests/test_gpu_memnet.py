@@ -6,7 +6,6 @@ import os
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
@@ -36,9 +35,7 @@ def load(name):
     return {k: (torch.from_numpy(z[k]) if z[k].dtype.kind in "fiu" else z[k]) for k in z.files}
 
 
-def rel(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return ((a - b).abs().max() / b.abs().max().clamp_min(1e-30)).item()
+from bn_float64 import check_batchnorm_vs_float64, rel  # noqa: E402  (the flow tests/test_gpu_launch_plans.py runs too)
 
 
 @pytest.mark.parametrize("shape,C", [((2, 24, 20), 64), ((1, 7, 9), 128), ((3, 16, 16), 1), ((1, 5, 13), 1),
@@ -46,41 +43,7 @@ def rel(a, b):
 def test_batchnorm_kernels_vs_float64(shape, C):
     """srhip_bn_stats / _apply / _bwd on channels-last data against nn.functional.batch_norm in float64 (training mode:
     batch statistics, running-statistics update, ReLU, gradients of x, gamma, beta with a skip gradient added)."""
-    from srhip import ops
-    gen = torch.Generator().manual_seed(C + shape[1])
-    B, H, W = shape
-    x = torch.randn(B, H, W, C, generator=gen) * 1.7 + 0.4
-    gamma, beta = 1 + 0.2 * torch.randn(C, generator=gen), 0.3 * torch.randn(C, generator=gen)
-    rm0, rv0 = 0.1 * torch.randn(C, generator=gen), 1 + 0.3 * torch.rand(C, generator=gen)
-    dy, res = torch.randn(B, H, W, C, generator=gen), torch.randn(B, H, W, C, generator=gen)
-    # float64 reference (NCHW)
-    xd = x.permute(0, 3, 1, 2).double().requires_grad_(True)
-    gd, bd = gamma.double().requires_grad_(True), beta.double().requires_grad_(True)
-    rm, rv = rm0.double().clone(), rv0.double().clone()
-    yd = F.relu(F.batch_norm(xd, rm, rv, gd, bd, training=True, momentum=0.1, eps=1e-5))
-    yd.backward(dy.permute(0, 3, 1, 2).double())
-    # device
-    xc, dyc, resc = x.cuda(), dy.cuda(), res.cuda()
-    rmc, rvc = rm0.cuda(), rv0.cuda()
-    coef = torch.empty(4, C, device="cuda")
-    ops.bn_stats(xc, gamma.cuda(), beta.cuda(), coef, rmc, rvc, 0.1, 1e-5)
-    y = ops.bn_apply(xc, coef, relu=True)
-    assert rel(y.permute(0, 3, 1, 2), yd) < 2e-6
-    assert rel(rmc, rm) < 1e-6 and rel(rvc, rv) < 1e-6
-    dx = torch.full_like(xc, float("nan"))
-    dg, db = torch.full((C,), 7.0, device="cuda"), torch.full((C,), -3.0, device="cuda")
-    ops.bn_bwd(dyc, xc, coef, a=y, dx=dx, res=resc, dgamma=dg, dbeta=db)
-    assert rel(dx - resc, xd.grad.permute(0, 2, 3, 1)) < 5e-6
-    assert rel(dg, gd.grad) < 2e-6 and rel(db, bd.grad) < 2e-6
-    ops.bn_bwd(dyc, xc, coef, a=y, dgamma=dg, dbeta=db, accumulate=True)      # parameter gradients only, added
-    assert rel(dg, 2 * gd.grad) < 2e-6 and rel(db, 2 * bd.grad) < 2e-6
-    # eval form: coefficients from the running statistics, no ReLU
-    rstd = torch.rsqrt(rv0 + 1e-5)
-    ce = torch.stack([rm0, rstd, gamma * rstd, beta]).cuda()
-    ye = ops.bn_apply(xc, ce, relu=False)
-    yed = F.batch_norm(x.permute(0, 3, 1, 2).double(), rm0.double(), rv0.double(), gamma.double(), beta.double(),
-                       training=False, eps=1e-5)
-    assert rel(ye.permute(0, 3, 1, 2), yed) < 2e-6
+    check_batchnorm_vs_float64(shape, C)
 
 
 def test_batchnorm_rejects_unsupported_channel_counts():
