@@ -967,6 +967,26 @@ long srhip_metrics_ssim_lv_ws(int B, int H, int W, int border, int nth);
 int srhip_metrics_ssim_lv(const float* E, const float* Hh, int B, int H, int W, int border,
                           const int* thresholds_dev, int nth, int L, int inputs_are_levels, double* workspace,
                           double* out, void* stream);
+/* Multi-scale SSIM at L levels (--msssim; Wang, Simoncelli, Bovik 2003), M = 1 .. 5 scales, float64, no ROI.  This text is the
+ * definition:
+ *   both images go through Q_L (skipped if inputs_are_levels), are cropped by border, x = level / L in float64;
+ *   scale 1 is that pair; scale j + 1 is the 2x2 mean of scale j on the grid of F.avg_pool2d(x, 2, padding=(h % 2, w % 2)): an
+ *     odd extent gets one zero row / column IN FRONT, the zero counts in the divisor 4, the new extent is ceil(h / 2);
+ *   every scale uses the window of srhip_metrics_ssim_lv (11x11, sigma 1.5, valid positions, C1 = 1e-4, C2 = 9e-4):
+ *     cs = (2 sxy + C2) / (sxx + syy + C2), ss = (2 mx my + C1) / (mx^2 + my^2 + C1) * cs, v_j = mean(cs) for j < M and
+ *     v_M = mean(ss), over all map pixels;
+ *   MS-SSIM = prod_j max(v_j, 0)^w_j with 0^w = 0; weights_host (HOST, M doubles in (0, 1]) or NULL: the first M of (0.0448,
+ *     0.2856, 0.3001, 0.2363, 0.1333), as published for M = 5 and divided by their sum for M < 5;
+ *   after the crop both sides must be at least 10 * 2^(M-1) + 1 (161 for M = 5: 161 -> 81 -> 41 -> 21 -> 11).
+ * out[b][0] = MS-SSIM, out[b][1 .. M] = the unclamped v_1 .. v_M, fp64.  The pyramid is kept in the workspace as exact integer
+ * sums of levels (L * 4^4 < 2^24) and divided at use; every block stores its (sum cs, sum ss) and the last kernel adds them in a
+ * fixed order: two calls give the same bits.  M + 1 launches, no host synchronisation, no allocation.
+ * workspace doubles: srhip_metrics_msssim_lv_ws(B, H, W, border, M) (0: M is not 1 .. 5 or the image is too small);
+ * workspace_doubles is what the caller's buffer holds, and a shorter one is refused. */
+long srhip_metrics_msssim_lv_ws(int B, int H, int W, int border, int M);
+int srhip_metrics_msssim_lv(const float* E, const float* Hh, int B, int H, int W, int border, int L, int inputs_are_levels,
+                            int M, const double* weights_host, double* workspace, long workspace_doubles, double* out,
+                            void* stream);
 
 /* Weight (and bias) gradients of up to 40 3x3 convolutions of ONE shape -- the body of an
  * EDSR-style stack (network_nlsn.py:72-93,325-345 backward) -- in one contraction launch plus one

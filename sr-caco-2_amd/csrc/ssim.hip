@@ -8,29 +8,12 @@
 #include "common.h"
 #include "kernels.h"
 #include "levels.h"
+#include "ssim_taps.h"
 
 namespace {
 
 constexpr int TS = 32;        // output tile edge
-constexpr int MAXWS = 19;     // largest window (README recipe uses 19)
 constexpr int TIN = TS + MAXWS - 1;
-
-struct Taps { float g[MAXWS]; };
-
-__host__ Taps gaussian_taps(int ws, bool centered_half) {
-  // loss: exp(-(i - ws//2)^2 / (2 sigma^2)) (ssim.py:23-27);
-  // metric: coords - (ks-1)/2 (utils_image.py:1102-1117) -- identical for odd ws
-  Taps t;
-  float g[MAXWS];
-  float s = 0.f;
-  for (int i = 0; i < ws; ++i) {
-    const float d = centered_half ? (float)i - (float)(ws - 1) / 2.0f : (float)(i - ws / 2);
-    g[i] = expf(-(d * d) / (2.0f * 1.5f * 1.5f));
-    s += g[i];
-  }
-  for (int i = 0; i < MAXWS; ++i) t.g[i] = i < ws ? g[i] / s : 0.f;
-  return t;
-}
 
 __device__ __forceinline__ float u8f(float v) {
   v = fminf(fmaxf(v, 0.f), 1.f) * 255.0f;

@@ -14,13 +14,17 @@ five metrics x all thresholds in two passes over the images).
 levels^2, PSNR is 20 log10(levels / sqrt(mse)), SSIM is on level / levels with float64 window moments, and ``inputs_are_u8``
 / the inputs of ``mbatch_gpu_calculate_*`` mean the levels 0 .. ``levels``.  The ROI stays ``Q_255(H) >= th``, the pixel set
 of the 8-bit metrics, whatever ``levels`` is.
+
+``msssim`` (not a reference argument; ``--msssim``): the number of scales, 1 .. 5, of the multi-scale SSIM of Wang, Simoncelli and
+Bovik (2003) that ``sweep`` adds under 'msssim'; include/srhip.h (srhip_metrics_msssim_lv) states it.  It is float64 at either
+white level, a whole-image metric without ROI slots, and needs both cropped sides to be at least 10 * 2^(scales - 1) + 1.
 """
 import torch
 
 from srhip import ops
 
 __all__ = ['tensor2uint82float', 'tensor2levels', 'mbatch_gpu_calculate_psnr', 'mbatch_gpu_calculate_mse',
-           'mbatch_gpu_calculate_nrmse', 'mbatch_gpu_calculate_ssim', 'sweep']
+           'mbatch_gpu_calculate_nrmse', 'mbatch_gpu_calculate_ssim', 'mbatch_gpu_calculate_msssim', 'sweep']
 
 
 def _need_cuda(t):
@@ -58,11 +62,12 @@ def _threshold_of(roi, img2, levels=255):
     return th
 
 
-def sweep(E, H, border=0, thresholds=(), inputs_are_u8=False, levels=255):
+def sweep(E, H, border=0, thresholds=(), inputs_are_u8=False, levels=255, msssim=0):
     """All metrics in two fused passes.  E, H: (B,1,h,w) in [0,1] (or already
     u8-valued floats; with ``levels``, floats that hold the levels 0 .. levels).  Returns dict name ->
     (B, 1+len(thresholds)) tensors; column 0 is 'no ROI', column k the ROI H_u8 >= thresholds[k-1].  ``levels`` other than
-    255: the float64 kernels at that white level (module docstring); 'ssim' is then float64."""
+    255: the float64 kernels at that white level (module docstring); 'ssim' is then float64.  ``msssim`` = M > 0: the dict gains
+    'msssim', the (B,) float64 multi-scale SSIM over M scales at ``levels``; the five other tensors are those of ``msssim=0``."""
     _need_cuda(E)
     assert E.shape == H.shape and E.ndim == 4 and E.shape[1] == 1, "1-channel images"
     E, H = E.float().contiguous(), H.float().contiguous()
@@ -72,8 +77,11 @@ def sweep(E, H, border=0, thresholds=(), inputs_are_u8=False, levels=255):
     else:
         fam = ops.metrics_psnr_family_lv(E, H, border, tuple(thresholds), levels, inputs_are_u8)
         ssim = ops.metrics_ssim_lv(E, H, border, tuple(thresholds), levels, inputs_are_u8)
-    return {"psnr": fam[:, :, 0], "psnr_y": fam[:, :, 1], "mse": fam[:, :, 2],
-            "nrmse": fam[:, :, 3], "ssim": ssim}
+    out = {"psnr": fam[:, :, 0], "psnr_y": fam[:, :, 1], "mse": fam[:, :, 2],
+           "nrmse": fam[:, :, 3], "ssim": ssim}
+    if msssim:
+        out["msssim"] = ops.metrics_msssim_lv(E, H, border, levels, msssim, inputs_are_u8)[:, 0].contiguous()
+    return out
 
 
 def _one(name, img1, img2, border, roi, levels=255):
@@ -102,3 +110,10 @@ def mbatch_gpu_calculate_nrmse(img, y, border=0, roi=None, levels=255):
 def mbatch_gpu_calculate_ssim(x, y, border=0, roi=None, levels=255):
     """utils_image.py:1120-1198; fp32 result."""
     return _one("ssim", x, y, border, roi, levels)
+
+
+def mbatch_gpu_calculate_msssim(x, y, border=0, levels=255, scales=5):
+    """(not a reference function) multi-scale SSIM over ``scales`` scales; inputs hold the levels 0 .. ``levels``; fp64 (B,)."""
+    _need_cuda(x)
+    assert x.ndim == 4 and x.shape == y.shape and x.shape[1] == 1, "1-channel images"
+    return ops.metrics_msssim_lv(x, y, border, levels, scales, True)[:, 0].contiguous()

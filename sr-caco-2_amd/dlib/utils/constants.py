@@ -76,6 +76,11 @@ PSNR_Y_MTR = 'psnr_y'
 SSIM_Y_MTR = 'ssim_y'      # listed by the reference (constants.py:118-131), never computed by its evaluation
 METRICS = [PSNR_MTR, SSIM_MTR, MSE_MTR, NRMSE_MTR, PSNR_Y_MTR, SSIM_Y_MTR]
 BEST_MTR = {PSNR_MTR: max, SSIM_MTR: max, MSE_MTR: min, NRMSE_MTR: min, PSNR_Y_MTR: max, SSIM_Y_MTR: max}
+# (not reference metrics) computed only when a run asks for them, so METRICS and the trackers of every other run keep their keys:
+# --msssim True, the multi-scale SSIM of Wang, Simoncelli and Bovik (2003); a whole-image metric, never in the ROI trackers
+MSSSIM_MTR = 'msssim'
+EXTRA_METRICS = [MSSSIM_MTR]
+EXTRA_BEST_MTR = {MSSSIM_MTR: max}
 
 # splits, tracker periods, fold files (reference constants.py:100-136,193,713)
 TRAIN_PHASE, EVAL_PHASE = 'train', 'eval'

@@ -161,6 +161,26 @@ def check_metric_levels(levels):
     return int(levels)
 
 
+def check_msssim(args):
+    """--msssim / --msssim_scales: the number of scales of the multi-scale SSIM this run computes, 1 .. 5 (default 5), or 0
+    without --msssim True; also what --model_select_mtr msssim needs"""
+    from dlib.utils import constants
+    on, scales = getattr(args, 'msssim', None), getattr(args, 'msssim_scales', None)
+    if not on:
+        if scales is not None:
+            raise ValueError(f'--msssim_scales {scales} needs --msssim True')
+        if getattr(args, 'model_select_mtr', None) == constants.MSSSIM_MTR:
+            raise ValueError(f'--model_select_mtr {constants.MSSSIM_MTR} needs --msssim True')
+        return 0
+    scales = 5 if scales is None else scales
+    if isinstance(scales, bool) or int(scales) != scales or not 1 <= scales <= 5:
+        raise ValueError(f'--msssim_scales {scales}: the number of scales is an integer in 1 .. 5')
+    if getattr(args, 'model_select_mtr', None) == constants.MSSSIM_MTR and getattr(args, 'eval_over_roi_also_model_select', False):
+        raise ValueError(f'--model_select_mtr {constants.MSSSIM_MTR} is a whole-image metric: it cannot select the model over the '
+                         f'ROI (--eval_over_roi_also_model_select True)')
+    return int(scales)
+
+
 LR_SYNTHS = ('bicubic', 'psf')
 LR_SYNTH_EVAL_SALT = 0x6C725F73796E7468        # + item index: the noise seed of a validation / test item under --lr_synth psf
 

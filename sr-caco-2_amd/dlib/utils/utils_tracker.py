@@ -24,8 +24,14 @@ __all__ = ['init_tracker', 'find_last_tracker', 'save_tracker', 'update_tracker_
            'write_current_perf_eval', 'current_perf_to_str']
 
 
-def _fresh_metrics() -> dict:
-    return {m: {'vals': [], 'best_val': 0.0} for m in constants.METRICS}
+def _fresh_metrics(extra=()) -> dict:
+    return {m: {'vals': [], 'best_val': 0.0} for m in list(constants.METRICS) + list(extra)}
+
+
+def extra_metrics(args, roi: bool = False) -> list:
+    """the metrics beyond constants.METRICS that this run computes: 'msssim' under --msssim True, a whole-image metric that the
+    ROI tracker never holds.  Without the option: none, and the trackers keep the reference's keys."""
+    return [constants.MSSSIM_MTR] if getattr(args, 'msssim', None) and not roi else []
 
 
 def _scalar(v):
@@ -36,15 +42,16 @@ def _scalar(v):
     return v
 
 
-def init_tracker(args) -> dict:
+def init_tracker(args, roi: bool = False) -> dict:
+    extra = extra_metrics(args, roi)
     out = {constants.TRAINSET: {constants.PR_EPOCH: dict(), constants.PR_ITER: dict()}}
     for split, names in ((constants.VALIDSET, args.valid_dsets), (constants.TESTSET, args.test_dsets)):
         out[split] = {}
         subsets = names.split(constants.SEP)
         for s in subsets:                                        # the model's rows first ...
-            out[split][s] = _fresh_metrics()
+            out[split][s] = _fresh_metrics(extra)
         for s in subsets:                                        # ... then the interpolation baseline's
-            out[split][f'{s}_{args.basic_interpolation}'] = _fresh_metrics()
+            out[split][f'{s}_{args.basic_interpolation}'] = _fresh_metrics(extra)
     return out
 
 
@@ -60,7 +67,7 @@ def find_last_tracker(save_dir: str, args) -> Tuple[dict, dict]:
             return loaded[0], loaded[1]
         except Exception:          # same policy as the reference: start over
             pass
-    return init_tracker(args), init_tracker(args)
+    return init_tracker(args), init_tracker(args, roi=True)
 
 
 def save_tracker(save_dir: str, tracker: dict, roi_tracker: dict):
@@ -78,7 +85,7 @@ def update_tracker_eval(tracker: dict, split: str, ds_name: str, metric: str, va
     """Append ``value``.  idx_best None: this metric decides -- best_val = BEST_MTR(metric)(value, best)
     and the index of its LAST occurrence is returned; else best_val = vals[idx_best] (the slave metrics
     follow the master metric's best evaluation)."""
-    assert split in (constants.VALIDSET, constants.TESTSET) and metric in constants.METRICS
+    assert split in (constants.VALIDSET, constants.TESTSET) and metric in constants.METRICS + constants.EXTRA_METRICS
     v = _scalar(value)
     node = tracker[split][ds_name]
     if metric not in node:
@@ -87,7 +94,7 @@ def update_tracker_eval(tracker: dict, split: str, ds_name: str, metric: str, va
     rec = node[metric]
     rec['vals'].append(v)
     if idx_best is None:
-        rec['best_val'] = constants.BEST_MTR[metric](v, rec['best_val'])
+        rec['best_val'] = {**constants.BEST_MTR, **constants.EXTRA_BEST_MTR}[metric](v, rec['best_val'])
         return tracker, _last_index_of(rec['vals'], rec['best_val'])
     rec['best_val'] = rec['vals'][idx_best]
     return tracker, None
@@ -95,7 +102,8 @@ def update_tracker_eval(tracker: dict, split: str, ds_name: str, metric: str, va
 
 def reset_tracker_eval(tracker: dict, split: str, ds_name: str) -> dict:
     assert split == constants.TESTSET, split      # test performance is not tracked over time
-    tracker[split][ds_name].update(_fresh_metrics())
+    node = tracker[split][ds_name]
+    node.update(_fresh_metrics([m for m in constants.EXTRA_METRICS if m in node]))
     return tracker
 
 
@@ -138,11 +146,11 @@ def write_current_perf_eval(tracker: dict, split: str, ds_name: str, save_dir, n
 def current_perf_to_str(status: dict, roi_status, master_mtr: str, model_select_roi: bool) -> str:
     lines = [f"CURRENT. EPO: {status['current_epoch']}. STEP: {status['current_step']}.",
              f"Dataset: {status['dataset']}.  Split: {status['split']}"]
-    for m in constants.METRICS:
+    for m in constants.METRICS + constants.EXTRA_METRICS:
         if f'last_{m}' not in status:
             continue
         tail = ' ---> MASTER' if m == master_mtr else ''
-        if roi_status is None:
+        if roi_status is None or f'last_{m}' not in roi_status:        # (a whole-image metric has no ROI value)
             lines.append(f"{m}: {status[f'best_{m}']:<.6f} [BEST] | {status[f'last_{m}']:<.4f} [LAST]{tail}")
         else:
             a, r = ('', '*') if model_select_roi else ('*', '')

@@ -154,7 +154,11 @@ def _fast_update_tracker(args, tracker, mtr_val, split, ds_name, idx_best=None):
     """master metric first (it fixes the index of the best evaluation), the others follow
     (utils_trainer.py:764-798)."""
     master = args.model_select_mtr
-    tracker, found = update_tracker_eval(tracker, split, ds_name, master, mtr_val[master], idx_best)
+    found = None
+    if master in mtr_val:
+        tracker, found = update_tracker_eval(tracker, split, ds_name, master, mtr_val[master], idx_best)
+    else:                              # the ROI tracker under a whole-image master metric (msssim): it only follows
+        assert idx_best is not None, master
     best = idx_best if idx_best is not None else found
     for k in mtr_val:
         if k != master:
@@ -173,14 +177,19 @@ def fast_eval(model, data_loader, ds_name: str, split: str, tracker: dict, roi_t
         reset_tracker_eval(roi_tracker, split, ds_name)
     model.set_eval_mode()
     border = args.scale
-    from dlib.utils.utils_dataloaders import check_metric_levels
+    from dlib.utils.utils_dataloaders import check_metric_levels, check_msssim
     # --metric_levels: the sweep at another white level; not given, today's call
-    full_depth = {} if check_metric_levels(getattr(args, 'metric_levels', None)) == 255 else {'levels': int(args.metric_levels)}
+    sweep_opts = {} if check_metric_levels(getattr(args, 'metric_levels', None)) == 255 else {'levels': int(args.metric_levels)}
+    # --msssim True: the sweep adds the multi-scale SSIM, a whole-image metric (no ROI slots); not given, today's call and keys
+    n_scales = check_msssim(args)
+    if n_scales:
+        sweep_opts['msssim'] = n_scales
+    mtrs = _MTRS + ((constants.MSSSIM_MTR,) if n_scales else ())
     with_roi = bool(args.eval_over_roi_also)
     ths = tuple(int(t) for t in args.eval_over_roi_also_ths) if with_roi else ()
     if with_roi:
         assert len(ths) > 0
-    sums = {m: 0.0 for m in _MTRS}
+    sums = {m: 0.0 for m in mtrs}
     roi_sums = {m: 0.0 for m in _MTRS}
     details, roi_details = {}, {}
     seen = 0
@@ -193,17 +202,24 @@ def fast_eval(model, data_loader, ds_name: str, split: str, tracker: dict, roi_t
         else:
             model = _forward_with_padding(test_data, model, args)
         vis = model.current_visuals()
+        if n_scales:
+            from srhip.ops import msssim_min_side
+            if min(vis['H'].shape[-2:]) < msssim_min_side(n_scales, border):
+                raise ValueError(f"--msssim True with --msssim_scales {n_scales}: image {test_data['h_id'][0]} of {ds_name} is "
+                                 f"{vis['H'].shape[-2]} x {vis['H'].shape[-1]}; both sides must be at least "
+                                 f"{msssim_min_side(n_scales, border)} (10 * 2^(scales - 1) + 1, and the border of {border} on "
+                                 f"every side)")
         with torch.no_grad():
-            sw = metrics.sweep(vis['E'], vis['H'], border=border, thresholds=ths, **full_depth)
-        host = {m: sw[m].double().cpu() for m in _MTRS}            # (B, 1 + nth)
-        for m in _MTRS:
+            sw = metrics.sweep(vis['E'], vis['H'], border=border, thresholds=ths, **sweep_opts)
+        host = {m: sw[m].double().cpu().reshape(sw[m].shape[0], -1) for m in mtrs}            # (B, 1 + nth); msssim (B, 1)
+        for m in mtrs:
             _check_finite_nonneg(host[m], m)
             sums[m] += host[m][:, 0].sum().item()
-            if with_roi:
+            if with_roi and m in _MTRS:
                 roi_sums[m] += host[m][:, 1:].mean(dim=1).sum().item()
         for i, img_id in enumerate(test_data['h_id']):
             assert img_id not in details, img_id
-            details[img_id] = {m: host[m][i, 0].item() for m in _MTRS}
+            details[img_id] = {m: host[m][i, 0].item() for m in mtrs}
             if with_roi:
                 roi_details[img_id] = {m: host[m][i, 1:].mean().item() for m in _MTRS}
             if seen + i < nbr_to_plot and getattr(args, 'is_master', True) and save_img_dir:
@@ -218,25 +234,25 @@ def fast_eval(model, data_loader, ds_name: str, split: str, tracker: dict, roi_t
     if getattr(args, 'distributed', False) and args.eval_bsize > 1:      # rank-sharded evaluation
         from dlib.utils.utils_parallel import sync_metric_sums, sync_dict_across_gpus
         dev = model.device if hasattr(model, 'device') else torch.device('cuda')
-        packed = {f'a/{m}': torch.tensor(sums[m], dtype=torch.float64, device=dev) for m in _MTRS}
+        packed = {f'a/{m}': torch.tensor(sums[m], dtype=torch.float64, device=dev) for m in mtrs}
         packed.update({f'r/{m}': torch.tensor(roi_sums[m], dtype=torch.float64, device=dev) for m in _MTRS})
         tot, n = sync_metric_sums(packed, n)                              # ONE collective for all sums
-        sums = {m: tot[f'a/{m}'].item() for m in _MTRS}
+        sums = {m: tot[f'a/{m}'].item() for m in mtrs}
         roi_sums = {m: tot[f'r/{m}'].item() for m in _MTRS}
         ids = data_loader.dataset.im_h_ids_to_float
 
-        def gather(det):
+        def gather(det, names):
             out = {}
-            for m in _MTRS:
+            for m in names:
                 g = sync_dict_across_gpus({ids[k]: torch.tensor(v[m], dtype=torch.float64, device=dev)
                                            for k, v in det.items()}, move_sync_vals_to_cpu=True)
                 for fid, val in g.items():
                     out.setdefault(data_loader.dataset.float_to_im_h_ids[fid], {})[m] = val.item()
             return out
-        details = gather(details)
+        details = gather(details, mtrs)
         if with_roi:
-            roi_details = gather(roi_details)
-    mtr_val = {m: sums[m] / n for m in _MTRS}
+            roi_details = gather(roi_details, _MTRS)
+    mtr_val = {m: sums[m] / n for m in mtrs}
     roi_mtr_val = {m: roi_sums[m] / n for m in _MTRS}
     DLLogger.log(f'Eval time Split: {split}, dataset: {ds_name}:  {_dt.datetime.now() - t0}')
     if not with_roi:

@@ -4,7 +4,7 @@
 
     python eval.py --cudaid 0 --exp_path <folder> [--data_root <datasets>] [--splits_root <folds>]
                    [--test_mode {0..4} [--test_refield 32] [--test_min_size 256]] [--in_max N]
-                   [--metric_levels N]
+                   [--metric_levels N] [--msssim True [--msssim_scales M]]
 
 <folder> is a reference-format experiment directory: ``config_model.yml`` (the yaml dump of the
 run's args, utils_parser.py:1397-1401) and ``best-models/G-model.pth`` (raw ``state_dict``,
@@ -34,9 +34,17 @@ from dlib.utils import constants  # noqa: E402
 import dlib.dllogger as DLLogger  # noqa: E402
 from dlib.utils.tools import Dict2Obj  # noqa: E402
 from dlib.models.select_model import define_model  # noqa: E402
-from dlib.utils.utils_dataloaders import get_all_eval_loaders  # noqa: E402
+from dlib.utils.utils_dataloaders import get_all_eval_loaders, check_msssim  # noqa: E402
 from dlib.utils.utils_trainer import evaluate  # noqa: E402
 from dlib.utils.utils_tracker import find_last_tracker, save_tracker  # noqa: E402
+
+
+def str2bool(v):
+    if v.lower() in ('true', '1', 'yes'):
+        return True
+    if v.lower() in ('false', '0', 'no'):
+        return False
+    raise argparse.ArgumentTypeError(f'boolean expected, got {v!r}')
 
 
 def load_args(argv=None):
@@ -58,6 +66,12 @@ def load_args(argv=None):
                     help="white level the metrics quantise prediction and target to, 255 .. 65535 (default: the one the run "
                          "recorded in config_model.yml, else 255: the reference's 8-bit-level metrics); the bicubic baseline "
                          "row is measured at the same level")
+    ap.add_argument("--msssim", type=str2bool, default=None,
+                    help="also compute the multi-scale SSIM (Wang, Simoncelli, Bovik 2003) of the net and of the bicubic baseline "
+                         "row (default: what the run recorded in config_model.yml, else off)")
+    ap.add_argument("--msssim_scales", type=int, default=None,
+                    help="--msssim True: the number of scales, 1 .. 5 (default: the run's, else 5); both sides of an evaluation "
+                         "image, the border excluded, must be at least 10 * 2^(scales - 1) + 1")
     ns = ap.parse_args(argv)
     if ns.in_max is not None and not 1 <= ns.in_max <= 65535:
         ap.error(f"--in_max {ns.in_max}: the white level of 16-bit tiles is an integer in 1 .. 65535")
@@ -72,6 +86,13 @@ def load_args(argv=None):
         args.in_max = ns.in_max
     if ns.metric_levels is not None:
         args.metric_levels = ns.metric_levels
+    for k in ('msssim', 'msssim_scales'):
+        if getattr(ns, k) is not None:
+            args[k] = getattr(ns, k)
+    try:
+        check_msssim(args)
+    except ValueError as e:
+        ap.error(str(e))
     if ns.data_root is None:
         raise SystemExit("eval.py: give --data_root (or SRHIP_DATA_ROOT): the parent of the dataset folders")
     args.data_root = ns.data_root

@@ -186,6 +186,13 @@ def parse_input(argv=None):
     # that white level, SSIM in float64 (dlib.metrics.sweep); the ROIs stay defined at the 8-bit levels.  A key of the
     # configuration and of config_model.yml -- where eval.py finds it, and a resumed run checks it -- only when given.
     ap.add_argument('--metric_levels', type=int, default=None)
+    # (not reference options) --msssim True: every evaluation also computes the multi-scale SSIM of Wang, Simoncelli and Bovik
+    # (2003) over --msssim_scales scales (1 .. 5, default 5), in float64 at the white level of the metrics (include/srhip.h states
+    # it): 'msssim' in the tracker, details_*.yml, the best-model yaml files and the log, never in the ROI files; and
+    # --model_select_mtr msssim becomes possible.  Keys of the configuration and of config_model.yml -- where eval.py finds them,
+    # and a resumed run checks them -- only when given.
+    ap.add_argument('--msssim', type=str2bool, default=None)
+    ap.add_argument('--msssim_scales', type=int, default=None)
     # (not a reference option) how the LR image of an HR-only pair is made: 'bicubic' (default: util.imresize_np, the
     # reference's) or 'psf', a camera model -- clean = bin_s(G_sigma * HR) with sigma in HR pixels, then per training batch
     # LR = (Poisson(photons * clean) + read_std * N(0, 1)) / photons with photons the expected count at white level and read_std
@@ -277,6 +284,11 @@ def parse_input(argv=None):
             cfg['train'][k] = v
         elif not k.startswith(nt + '_'):
             cfg[k] = v
+    from dlib.utils.utils_dataloaders import check_msssim
+    try:
+        check_msssim(Dict2Obj(cfg))
+    except ValueError as e:
+        ap.error(str(e))
     if cfg['method'] != constants.NETTYPE_METHOD[net_type]:
         raise ValueError(f"--method {cfg['method']} does not match --net_type {net_type} "
                          f"({constants.NETTYPE_METHOD[net_type]})")
@@ -325,7 +337,7 @@ def _resume_point(args):
         except Exception:                       # python-tagged values the safe loader refuses: compare the text
             old = {}
             txt = open(cfg_path).read()
-            for key in ('net_type', 'scale', 'metric_levels'):
+            for key in ('net_type', 'scale', 'metric_levels', 'msssim', 'msssim_scales'):
                 import re
                 m = re.search(rf'^{key}:\s*(\S+)', txt, re.M)
                 if m:
@@ -334,7 +346,11 @@ def _resume_point(args):
             old['net_type'] = old['netG']['net_type']           # (the reference's own files keep it under netG)
         # metric_levels, absent meaning 255: a tracker that mixed 8-bit and full-depth PSNRs would select a wrong best model
         old.setdefault('metric_levels', 255)
-        asked = {'net_type': args.net_type, 'scale': args.scale, 'metric_levels': getattr(args, 'metric_levels', None) or 255}
+        # msssim_scales, 0 meaning a run without --msssim True: its tracker would gain or lose the key
+        from dlib.utils.utils_dataloaders import check_msssim
+        old['msssim_scales'] = int(old.get('msssim_scales') or 5) if str(old.pop('msssim', None)).lower() == 'true' else 0
+        asked = {'net_type': args.net_type, 'scale': args.scale, 'metric_levels': getattr(args, 'metric_levels', None) or 255,
+                 'msssim_scales': check_msssim(args)}
         for key, want in asked.items():
             if key in old and str(old[key]) != str(want):
                 raise SystemExit(f"--outd {args.outd_backup} holds an experiment with {key} = {old[key]} (config_model.yml); this "
@@ -452,7 +468,10 @@ def main(argv=None):
     model = _forward_with_padding(batch, model, args)          # SwinIR: flipped-strip padding to the next window multiple
     vis = model.current_visuals()
     ths = tuple(args.eval_over_roi_also_ths) if args.eval_over_roi_also else ()
-    sw = metrics.sweep(vis['E'], vis['H'], border=args.scale, thresholds=ths, levels=args.metric_levels or 255)
+    from dlib.utils.utils_dataloaders import check_msssim
+    n_scales = check_msssim(args)
+    sw = metrics.sweep(vis['E'], vis['H'], border=args.scale, thresholds=ths, levels=args.metric_levels or 255,
+                       **({'msssim': n_scales} if n_scales else {}))
     if rank == 0:
         for k in (constants.PSNR_MTR, constants.PSNR_Y_MTR, constants.MSE_MTR, constants.NRMSE_MTR,
                   constants.SSIM_MTR):
@@ -461,6 +480,8 @@ def main(argv=None):
             if ths:
                 msg += f'   ROI(avg over th {list(ths)}) {sw[k][:, 1:].double().mean().item():.4f}'
             print(msg)
+        if n_scales:
+            print(f"{constants.MSSSIM_MTR:8s} {sw[constants.MSSSIM_MTR].mean().item():.4f}   ({n_scales} scales)")
         if args.max_iters > current_step:
             print('saved', model.save(args.max_iters))                  # <iter>_G.pth + <iter>_optimizerG.pth
             clean_previous_checkpoints_except_last(model.save_dir, ['G', 'optimizerG'] + (['E'] if model.E_decay > 0 else []))

@@ -2338,6 +2338,38 @@ def metrics_ssim_lv(E, Hh, border, thresholds=(), levels=65535, inputs_are_level
     return out
 
 
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)       # Wang, Simoncelli, Bovik 2003
+
+
+def msssim_weights(scales):
+    """the first ``scales`` of the published weights: as published for 5, divided by their sum for fewer"""
+    if isinstance(scales, bool) or int(scales) != scales or not 1 <= scales <= 5:
+        raise ValueError(f"msssim: the number of scales {scales} is outside 1 .. 5")
+    w = MSSSIM_WEIGHTS[:int(scales)]
+    return w if scales == 5 else tuple(v / sum(w) for v in w)
+
+
+def msssim_min_side(scales, border=0):
+    """the smallest side an image may have under ``scales`` scales, the border on both ends included"""
+    return 10 * 2 ** (int(scales) - 1) + 1 + 2 * int(border)
+
+
+def metrics_msssim_lv(E, Hh, border, levels=255, scales=5, inputs_are_levels=False):
+    """multi-scale SSIM at ``levels`` grey levels in float64 (include/srhip.h states it): fp64 [B, 1 + scales] = MS-SSIM, then the
+    unclamped v_1 .. v_scales (mean cs of every scale but the last, mean ss of the last)"""
+    _chk(E, Hh)
+    E, Hh = E.float().contiguous(), Hh.float().contiguous()
+    B = E.shape[0]
+    H, W = E.shape[-2:]
+    w = (ctypes.c_double * int(scales))(*msssim_weights(scales))
+    n = max(lib.srhip_metrics_msssim_lv_ws(B, H, W, border, scales), 1)
+    ws = SCRATCH.get("msssim_lv_ws", n, torch.float64, E.device)
+    out = torch.empty(B, scales + 1, dtype=torch.float64, device=E.device)
+    call("srhip_metrics_msssim_lv", _p(E), _p(Hh), B, H, W, border, _levels(levels, "metrics_msssim_lv"), int(inputs_are_levels),
+         int(scales), ctypes.cast(w, ctypes.c_void_p), _p(ws), ws.numel(), _p(out), _st())
+    return out
+
+
 # ------------------------------------------------------------------ optimizers
 def adam_step(p, g, m, v, step, lr, b1=0.9, b2=0.999, eps=1e-8, wd=0.0, gscale=1.0, skip_flag=None):
     _chk(p, g, m, v, skip_flag)
