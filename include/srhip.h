@@ -987,6 +987,31 @@ long srhip_metrics_msssim_lv_ws(int B, int H, int W, int border, int M);
 int srhip_metrics_msssim_lv(const float* E, const float* Hh, int B, int H, int W, int border, int L, int inputs_are_levels,
                             int M, const double* weights_host, double* workspace, long workspace_doubles, double* out,
                             void* stream);
+/* Fourier ring correlation of E (prediction) against Hh (target) at L levels (--frc; Saxton & Baumeister 1982, Nieuwenhuizen et
+ * al. 2013), [B][H][W] single-channel images, float64.  This text is the definition:
+ *   1. both images go through Q_L (skipped if inputs_are_levels), x = level / L in float64;
+ *   2. NO border crop: S is the largest power of two not above min(H, W), at most 2048; both images are cut to the centred
+ *      S x S square at the offsets (H - S) / 2 and (W - S) / 2 (integer division); S < 32 is refused;
+ *   3. window: separable periodic Hann, win[i] = 0.5 - 0.5 cos(2 pi i / S), no mean subtraction (zero at the edge, it weighs
+ *      the frame the other metrics crop below 0.3 %);
+ *   4. F1 = FFT2(win x_E), F2 = FFT2(win x_H), unnormalised;
+ *   5. rings: with the signed integer frequencies kx, ky in [-S/2, S/2) the ring of k is the integer r with
+ *      (2r - 1)^2 <= 4 |k|^2 < (2r + 1)^2 and r = 0 for k = 0 (integer arithmetic; |k| = r + 1/2 has no integer solution, so
+ *      there is no tie); the rings 0 .. S/2 are kept, the corners beyond are dropped;
+ *   6. C_r = sum Re(F1 conj F2), P1_r = sum |F1|^2, P2_r = sum |F2|^2 over the ring; FRC[r] = C_r / sqrt(P1_r P2_r), and 0
+ *      where the product is 0;
+ *   7. cutoff at the threshold T (1.0 / 7.0 by convention), searched from r = 1: at the first r with FRC[r] < T let
+ *      p = FRC[r - 1]; the crossing is x = 0 if p < T, else x = (r - 1) + (p - T) / (p - FRC[r]); with no such r, x = S/2;
+ *      cut = x / (S/2) in [0, 1], the cutoff as a fraction of Nyquist (higher is better; the resolution in pixels is 2 / cut).
+ *      The curve is NOT smoothed before the search (the literature often fits a LOESS first).
+ * curve[b][0 .. S/2] = FRC, cut[b], fp64.  One complex transform per pair (z = win x_E + i win x_H; F1 and F2 from Z(k) and
+ * Z(-k)), radix-2 in LDS; every ring's terms are added in a fixed order and nothing is accumulated with atomics: two calls give
+ * the same bits.  Three launches, no host synchronisation, no allocation.
+ * workspace doubles: srhip_metrics_frc_lv_ws(B, H, W) (0: a side is below 32); workspace_doubles is what the caller's buffer
+ * holds, and a shorter one is refused, as is a threshold outside (0, 1); the workspace is 16-byte aligned. */
+long srhip_metrics_frc_lv_ws(int B, int H, int W);
+int srhip_metrics_frc_lv(const float* E, const float* Hh, int B, int H, int W, int L, int inputs_are_levels, double threshold,
+                         double* workspace, long workspace_doubles, double* curve, double* cut, void* stream);
 
 /* Weight (and bias) gradients of up to 40 3x3 convolutions of ONE shape -- the body of an
  * EDSR-style stack (network_nlsn.py:72-93,325-345 backward) -- in one contraction launch plus one

@@ -18,13 +18,19 @@ of the 8-bit metrics, whatever ``levels`` is.
 ``msssim`` (not a reference argument; ``--msssim``): the number of scales, 1 .. 5, of the multi-scale SSIM of Wang, Simoncelli and
 Bovik (2003) that ``sweep`` adds under 'msssim'; include/srhip.h (srhip_metrics_msssim_lv) states it.  It is float64 at either
 white level, a whole-image metric without ROI slots, and needs both cropped sides to be at least 10 * 2^(scales - 1) + 1.
+
+``frc`` / ``mbatch_gpu_calculate_frc`` (not reference functions; ``--frc``): the Fourier ring correlation of prediction against
+target and its cutoff, the resolution figure of the light-microscopy literature; include/srhip.h (srhip_metrics_frc_lv) states it.
+A call of its own, never part of ``sweep``: a report metric, not a tracker metric.  No border crop (a Hann window instead), the
+centred power-of-two square, float64; both sides at least 32.
 """
 import torch
 
 from srhip import ops
 
 __all__ = ['tensor2uint82float', 'tensor2levels', 'mbatch_gpu_calculate_psnr', 'mbatch_gpu_calculate_mse',
-           'mbatch_gpu_calculate_nrmse', 'mbatch_gpu_calculate_ssim', 'mbatch_gpu_calculate_msssim', 'sweep']
+           'mbatch_gpu_calculate_nrmse', 'mbatch_gpu_calculate_ssim', 'mbatch_gpu_calculate_msssim', 'sweep',
+           'frc', 'mbatch_gpu_calculate_frc']
 
 
 def _need_cuda(t):
@@ -117,3 +123,20 @@ def mbatch_gpu_calculate_msssim(x, y, border=0, levels=255, scales=5):
     _need_cuda(x)
     assert x.ndim == 4 and x.shape == y.shape and x.shape[1] == 1, "1-channel images"
     return ops.metrics_msssim_lv(x, y, border, levels, scales, True)[:, 0].contiguous()
+
+
+def frc(E, H, levels=255, threshold=ops.FRC_THRESHOLD, inputs_are_u8=False):
+    """(not a reference function) Fourier ring correlation of E against H, (B,1,h,w) in [0,1] (or, with ``inputs_are_u8``, floats
+    that hold the levels 0 .. ``levels``).  Returns {'curve': (B, S/2 + 1) float64 over the rings 0 .. S/2, 'cut': (B,) float64,
+    the first crossing of ``threshold`` as a fraction of Nyquist (2 / cut is the resolution in pixels), 'side': S}."""
+    _need_cuda(E)
+    assert E.shape == H.shape and E.ndim == 4 and E.shape[1] == 1, "1-channel images"
+    curve, cut = ops.metrics_frc_lv(E, H, levels, threshold, inputs_are_u8)
+    return {"curve": curve, "cut": cut, "side": ops.frc_side(*E.shape[-2:])}
+
+
+def mbatch_gpu_calculate_frc(x, y, levels=255, threshold=ops.FRC_THRESHOLD):
+    """(not a reference function) the cutoff of the Fourier ring correlation; inputs hold the levels 0 .. ``levels``; fp64 (B,)."""
+    _need_cuda(x)
+    assert x.ndim == 4 and x.shape == y.shape and x.shape[1] == 1, "1-channel images"
+    return ops.metrics_frc_lv(x, y, levels, threshold, True)[1]

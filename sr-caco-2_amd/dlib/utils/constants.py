@@ -81,6 +81,10 @@ BEST_MTR = {PSNR_MTR: max, SSIM_MTR: max, MSE_MTR: min, NRMSE_MTR: min, PSNR_Y_M
 MSSSIM_MTR = 'msssim'
 EXTRA_METRICS = [MSSSIM_MTR]
 EXTRA_BEST_MTR = {MSSSIM_MTR: max}
+# (not a reference metric) --frc True: the cutoff of the Fourier ring correlation as a fraction of Nyquist.  A REPORT metric: in
+# details_*.yml, frc_*.yml and the log, never in METRICS, EXTRA_METRICS, a tracker or --model_select_mtr
+FRC_CUT = 'frc_cut'
+REPORT_METRICS = [FRC_CUT]
 
 # splits, tracker periods, fold files (reference constants.py:100-136,193,713)
 TRAIN_PHASE, EVAL_PHASE = 'train', 'eval'

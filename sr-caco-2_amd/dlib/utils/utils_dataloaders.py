@@ -181,6 +181,25 @@ def check_msssim(args):
     return int(scales)
 
 
+def check_frc(args):
+    """--frc / --frc_threshold: the threshold of the Fourier ring correlation cutoff this run reports, a number in (0, 1) (default
+    1 / 7), or 0 without --frc True.  The cutoff is a report metric, a threshold crossing that is discontinuous in the weights:
+    --model_select_mtr frc_cut is refused by name, with or without the option"""
+    from dlib.utils import constants
+    on, thr = getattr(args, 'frc', None), getattr(args, 'frc_threshold', None)
+    if getattr(args, 'model_select_mtr', None) == constants.FRC_CUT:
+        raise ValueError(f'--model_select_mtr {constants.FRC_CUT}: the cutoff of the Fourier ring correlation is a report metric '
+                         f'(--frc True), not a selection criterion')
+    if not on:
+        if thr is not None:
+            raise ValueError(f'--frc_threshold {thr} needs --frc True')
+        return 0
+    thr = 1.0 / 7.0 if thr is None else thr
+    if isinstance(thr, bool) or not isinstance(thr, (int, float)) or not 0.0 < thr < 1.0:
+        raise ValueError(f'--frc_threshold {thr}: the threshold is a number in (0, 1)')
+    return float(thr)
+
+
 LR_SYNTHS = ('bicubic', 'psf')
 LR_SYNTH_EVAL_SALT = 0x6C725F73796E7468        # + item index: the noise seed of a validation / test item under --lr_synth psf
 

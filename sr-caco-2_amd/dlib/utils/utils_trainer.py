@@ -166,18 +166,41 @@ def _fast_update_tracker(args, tracker, mtr_val, split, ds_name, idx_best=None):
     return tracker, best
 
 
+_FRC_SIDE = '_frc_side'     # rides in details[img_id] beside 'frc_cut' (through the rank gather) until _frc_report takes it out
+
+
+def _frc_report(threshold, mean_cut, details, curves):
+    """the content of best-models/frc_<ds>.yml: the threshold, the set's mean cutoff, per image the side of the transformed square,
+    the cutoff as a fraction of Nyquist and the resolution 2 / cut in HR pixels (null at cut 0), and the mean curve per side met;
+    ``curves`` None: a rank-sharded evaluation, which exchanges cutoffs but no curves.  Takes the side out of ``details``."""
+    images = {}
+    for img_id, d in details.items():
+        cut = d[constants.FRC_CUT]
+        images[img_id] = {'side': int(d.pop(_FRC_SIDE)), 'cut': cut, 'res_px': 2.0 / cut if cut > 0 else None}
+    out = {'threshold': float(threshold), 'mean_cut': float(mean_cut), 'images': images}
+    if curves is None:
+        out['mean_curve'] = None
+        out['mean_curve_note'] = 'not written by a rank-sharded evaluation: the ranks exchange cutoffs, not curves'
+    else:
+        out['mean_curve'] = {int(S): (tot / cnt).tolist() for S, (tot, cnt) in sorted(curves.items())}
+    return out
+
+
 def fast_eval(model, data_loader, ds_name: str, split: str, tracker: dict, roi_tracker: dict, args,
-              current_step: int, epoch: int, nbr_to_plot: int = 2, save_img_dir: str = ''):
+              current_step: int, epoch: int, nbr_to_plot: int = 2, save_img_dir: str = '', frc_report: dict = None):
     """One dataset: returns (tracker, details, roi_tracker, roi_details) with
     details[h_id] = {psnr, mse, nrmse, ssim, psnr_y} per image (ROI: averaged over the thresholds
-    eval_over_roi_also_ths, utils_trainer.py:874-930) and the dataset means appended to the trackers."""
+    eval_over_roi_also_ths, utils_trainer.py:874-930) and the dataset means appended to the trackers.
+    Under --frc True details[h_id] gains 'frc_cut', the set's mean cutoff goes to the log, and ``frc_report`` (a dict, if given)
+    is filled with what evaluate_single_ds writes to frc_<ds>.yml; no tracker and no ROI file sees any of it."""
     from dlib import metrics
     if split == constants.TESTSET:
         reset_tracker_eval(tracker, split, ds_name)
         reset_tracker_eval(roi_tracker, split, ds_name)
     model.set_eval_mode()
     border = args.scale
-    from dlib.utils.utils_dataloaders import check_metric_levels, check_msssim
+    from dlib.utils.utils_dataloaders import check_metric_levels, check_msssim, check_frc
+    from srhip.ops import FRC_MIN_SIDE
     # --metric_levels: the sweep at another white level; not given, today's call
     sweep_opts = {} if check_metric_levels(getattr(args, 'metric_levels', None)) == 255 else {'levels': int(args.metric_levels)}
     # --msssim True: the sweep adds the multi-scale SSIM, a whole-image metric (no ROI slots); not given, today's call and keys
@@ -185,6 +208,11 @@ def fast_eval(model, data_loader, ds_name: str, split: str, tracker: dict, roi_t
     if n_scales:
         sweep_opts['msssim'] = n_scales
     mtrs = _MTRS + ((constants.MSSSIM_MTR,) if n_scales else ())
+    # --frc True: one more call a batch, the Fourier ring correlation of the whole image.  A report metric: per-image cutoffs in
+    # the details, the mean in the log, never in a tracker; not given, today's calls and keys
+    frc_thr = check_frc(args)
+    frc_opts = {} if 'levels' not in sweep_opts else {'levels': sweep_opts['levels']}
+    frc_sum, frc_curves = 0.0, {}                           # sum of cutoffs; side -> [sum of curves, images]
     with_roi = bool(args.eval_over_roi_also)
     ths = tuple(int(t) for t in args.eval_over_roi_also_ths) if with_roi else ()
     if with_roi:
@@ -209,17 +237,31 @@ def fast_eval(model, data_loader, ds_name: str, split: str, tracker: dict, roi_t
                                  f"{vis['H'].shape[-2]} x {vis['H'].shape[-1]}; both sides must be at least "
                                  f"{msssim_min_side(n_scales, border)} (10 * 2^(scales - 1) + 1, and the border of {border} on "
                                  f"every side)")
+        if frc_thr and min(vis['H'].shape[-2:]) < FRC_MIN_SIDE:
+            raise ValueError(f"--frc True: image {test_data['h_id'][0]} of {ds_name} is {vis['H'].shape[-2]} x "
+                             f"{vis['H'].shape[-1]}; both sides must be at least {FRC_MIN_SIDE}")
         with torch.no_grad():
             sw = metrics.sweep(vis['E'], vis['H'], border=border, thresholds=ths, **sweep_opts)
+            fr = metrics.frc(vis['E'], vis['H'], threshold=frc_thr, **frc_opts) if frc_thr else None
         host = {m: sw[m].double().cpu().reshape(sw[m].shape[0], -1) for m in mtrs}            # (B, 1 + nth); msssim (B, 1)
         for m in mtrs:
             _check_finite_nonneg(host[m], m)
             sums[m] += host[m][:, 0].sum().item()
             if with_roi and m in _MTRS:
                 roi_sums[m] += host[m][:, 1:].mean(dim=1).sum().item()
+        if fr is not None:
+            cuts, curves = fr['cut'].cpu(), fr['curve'].cpu()
+            _check_finite_nonneg(cuts, constants.FRC_CUT)
+            frc_sum += cuts.sum().item()
+            acc = frc_curves.setdefault(fr['side'], [torch.zeros(curves.shape[1], dtype=torch.float64), 0])
+            acc[0] += curves.sum(dim=0)
+            acc[1] += curves.shape[0]
         for i, img_id in enumerate(test_data['h_id']):
             assert img_id not in details, img_id
             details[img_id] = {m: host[m][i, 0].item() for m in mtrs}
+            if fr is not None:
+                details[img_id][constants.FRC_CUT] = cuts[i].item()
+                details[img_id][_FRC_SIDE] = float(fr['side'])
             if with_roi:
                 roi_details[img_id] = {m: host[m][i, 1:].mean().item() for m in _MTRS}
             if seen + i < nbr_to_plot and getattr(args, 'is_master', True) and save_img_dir:
@@ -236,9 +278,13 @@ def fast_eval(model, data_loader, ds_name: str, split: str, tracker: dict, roi_t
         dev = model.device if hasattr(model, 'device') else torch.device('cuda')
         packed = {f'a/{m}': torch.tensor(sums[m], dtype=torch.float64, device=dev) for m in mtrs}
         packed.update({f'r/{m}': torch.tensor(roi_sums[m], dtype=torch.float64, device=dev) for m in _MTRS})
+        if frc_thr:
+            packed['f/cut'] = torch.tensor(frc_sum, dtype=torch.float64, device=dev)
         tot, n = sync_metric_sums(packed, n)                              # ONE collective for all sums
         sums = {m: tot[f'a/{m}'].item() for m in mtrs}
         roi_sums = {m: tot[f'r/{m}'].item() for m in _MTRS}
+        if frc_thr:
+            frc_sum = tot['f/cut'].item()
         ids = data_loader.dataset.im_h_ids_to_float
 
         def gather(det, names):
@@ -249,12 +295,19 @@ def fast_eval(model, data_loader, ds_name: str, split: str, tracker: dict, roi_t
                 for fid, val in g.items():
                     out.setdefault(data_loader.dataset.float_to_im_h_ids[fid], {})[m] = val.item()
             return out
-        details = gather(details, mtrs)
+        details = gather(details, mtrs + ((constants.FRC_CUT, _FRC_SIDE) if frc_thr else ()))
+        if frc_thr:                    # the cutoffs and sides travel with the details; the curves stay on their ranks
+            frc_curves = None
         if with_roi:
             roi_details = gather(roi_details, _MTRS)
     mtr_val = {m: sums[m] / n for m in mtrs}
     roi_mtr_val = {m: roi_sums[m] / n for m in _MTRS}
     DLLogger.log(f'Eval time Split: {split}, dataset: {ds_name}:  {_dt.datetime.now() - t0}')
+    if frc_thr:
+        DLLogger.log(f'{constants.FRC_CUT}: {frc_sum / n:<.6f} [MEAN over {ds_name}; fraction of Nyquist at FRC = {frc_thr:.6g}]')
+        report = _frc_report(frc_thr, frc_sum / n, details, frc_curves)
+        if frc_report is not None:
+            frc_report.update(report)
     if not with_roi:
         tracker, _ = _fast_update_tracker(args, tracker, mtr_val, split, ds_name)
     elif args.eval_over_roi_also_model_select:
@@ -270,15 +323,20 @@ def fast_eval(model, data_loader, ds_name: str, split: str, tracker: dict, roi_t
 def evaluate_single_ds(args, model, loader, ds_name: str, tracker: dict, roi_tracker: dict, current_step: int,
                        epoch: int, split: str, nbr_to_plot: int = 10, save_img_dir: str = ''):
     """fast_eval + the files of utils_trainer.py:1102-1181 under <outd_backup>/best-models:
-    details_<ds>.yml, roi_details_<ds>.yml, <ds>.yaml, roi-<ds>.yaml."""
+    details_<ds>.yml, roi_details_<ds>.yml, <ds>.yaml, roi-<ds>.yaml; under --frc True also frc_<ds>.yml (_frc_report)."""
     if not os.path.isdir(save_img_dir):
         save_img_dir = join(args.outd, args.save_dir_imgs, split, ds_name)
         os.makedirs(save_img_dir, exist_ok=True)
+    frc_report = {}
     tracker, details, roi_tracker, roi_details = fast_eval(
-        model, loader, ds_name, split, tracker, roi_tracker, args, current_step, epoch, nbr_to_plot, save_img_dir)
+        model, loader, ds_name, split, tracker, roi_tracker, args, current_step, epoch, nbr_to_plot, save_img_dir,
+        frc_report=frc_report)
     if getattr(args, 'is_master', True):
         d = join(args.outd_backup, 'best-models')
         os.makedirs(d, exist_ok=True)
+        if frc_report:                 # --frc True: a report of its own, beside the details
+            with open(join(d, f'frc_{ds_name}.yml'), 'w') as f:
+                yaml.dump(frc_report, f)
         with open(join(d, f'details_{ds_name}.yml'), 'w') as f:
             yaml.dump(details, f)
         status = write_current_perf_eval(tracker, split, ds_name, d, f'{ds_name}.yaml', current_step, epoch)

@@ -4,7 +4,7 @@
 
     python eval.py --cudaid 0 --exp_path <folder> [--data_root <datasets>] [--splits_root <folds>]
                    [--test_mode {0..4} [--test_refield 32] [--test_min_size 256]] [--in_max N]
-                   [--metric_levels N] [--msssim True [--msssim_scales M]]
+                   [--metric_levels N] [--msssim True [--msssim_scales M]] [--frc True [--frc_threshold T]]
 
 <folder> is a reference-format experiment directory: ``config_model.yml`` (the yaml dump of the
 run's args, utils_parser.py:1397-1401) and ``best-models/G-model.pth`` (raw ``state_dict``,
@@ -12,7 +12,8 @@ model_base.py:173-181).  Written, as by the reference, under ``<folder>/eval_tes
 ``log.txt``, ``log.json``, ``tracker.pkl``, ``roi_tracker.pkl``; under ``<folder>/best-models/``:
 ``details_<ds>.yml``, ``<ds>.yaml`` (+ ``roi_details_<ds>.yml``, ``roi-<ds>.yaml`` with
 --eval_over_roi_also) and the same four for the bicubic baseline row ``<ds>_bicubic``; predictions of the
-first images under ``<folder>/<save_dir_imgs>/test/<ds>/``.
+first images under ``<folder>/<save_dir_imgs>/test/<ds>/``.  With --frc True also ``best-models/frc_<ds>.yml`` for both rows: the
+Fourier ring correlation cutoff of every image, the set's mean and the mean curve.
 
 The reference resolves the dataset root from host-specific environment variables
 (utils_config.py:24-56); here it is ``--data_root`` / $SRHIP_DATA_ROOT, and the folds directory
@@ -34,7 +35,7 @@ from dlib.utils import constants  # noqa: E402
 import dlib.dllogger as DLLogger  # noqa: E402
 from dlib.utils.tools import Dict2Obj  # noqa: E402
 from dlib.models.select_model import define_model  # noqa: E402
-from dlib.utils.utils_dataloaders import get_all_eval_loaders, check_msssim  # noqa: E402
+from dlib.utils.utils_dataloaders import get_all_eval_loaders, check_msssim, check_frc  # noqa: E402
 from dlib.utils.utils_trainer import evaluate  # noqa: E402
 from dlib.utils.utils_tracker import find_last_tracker, save_tracker  # noqa: E402
 
@@ -72,6 +73,12 @@ def load_args(argv=None):
     ap.add_argument("--msssim_scales", type=int, default=None,
                     help="--msssim True: the number of scales, 1 .. 5 (default: the run's, else 5); both sides of an evaluation "
                          "image, the border excluded, must be at least 10 * 2^(scales - 1) + 1")
+    ap.add_argument("--frc", type=str2bool, default=None,
+                    help="also compute the Fourier ring correlation of prediction against target, for the net and for the bicubic "
+                         "baseline row: 'frc_cut' per image in details_*.yml, best-models/frc_<ds>.yml, the mean in the log "
+                         "(default: what the run recorded in config_model.yml, else off)")
+    ap.add_argument("--frc_threshold", type=float, default=None,
+                    help="--frc True: the threshold of the cutoff, in (0, 1) (default: the run's, else 1 / 7)")
     ns = ap.parse_args(argv)
     if ns.in_max is not None and not 1 <= ns.in_max <= 65535:
         ap.error(f"--in_max {ns.in_max}: the white level of 16-bit tiles is an integer in 1 .. 65535")
@@ -86,11 +93,14 @@ def load_args(argv=None):
         args.in_max = ns.in_max
     if ns.metric_levels is not None:
         args.metric_levels = ns.metric_levels
-    for k in ('msssim', 'msssim_scales'):
+    for k in ('msssim', 'msssim_scales', 'frc', 'frc_threshold'):
         if getattr(ns, k) is not None:
             args[k] = getattr(ns, k)
+    if ns.frc is False and ns.frc_threshold is None:
+        args.pop('frc_threshold', None)               # --frc False alone turns off a run recorded with a threshold of its own
     try:
         check_msssim(args)
+        check_frc(args)
     except ValueError as e:
         ap.error(str(e))
     if ns.data_root is None:

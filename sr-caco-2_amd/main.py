@@ -193,6 +193,13 @@ def parse_input(argv=None):
     # and a resumed run checks them -- only when given.
     ap.add_argument('--msssim', type=str2bool, default=None)
     ap.add_argument('--msssim_scales', type=int, default=None)
+    # (not reference options) --frc True: every evaluation also computes the Fourier ring correlation of prediction against target
+    # (include/srhip.h states it) and reports its cutoff at --frc_threshold (in (0, 1), default 1 / 7) as a fraction of Nyquist:
+    # 'frc_cut' per image in details_*.yml, the set mean in the log, best-models/frc_<ds>.yml with the mean curve.  A report
+    # metric: no tracker holds it and --model_select_mtr frc_cut is refused.  Keys of the configuration and of config_model.yml
+    # -- where eval.py finds them -- only when given; nothing a resumed run records depends on them.
+    ap.add_argument('--frc', type=str2bool, default=None)
+    ap.add_argument('--frc_threshold', type=float, default=None)
     # (not a reference option) how the LR image of an HR-only pair is made: 'bicubic' (default: util.imresize_np, the
     # reference's) or 'psf', a camera model -- clean = bin_s(G_sigma * HR) with sigma in HR pixels, then per training batch
     # LR = (Poisson(photons * clean) + read_std * N(0, 1)) / photons with photons the expected count at white level and read_std
@@ -284,9 +291,10 @@ def parse_input(argv=None):
             cfg['train'][k] = v
         elif not k.startswith(nt + '_'):
             cfg[k] = v
-    from dlib.utils.utils_dataloaders import check_msssim
+    from dlib.utils.utils_dataloaders import check_msssim, check_frc
     try:
         check_msssim(Dict2Obj(cfg))
+        check_frc(Dict2Obj(cfg))
     except ValueError as e:
         ap.error(str(e))
     if cfg['method'] != constants.NETTYPE_METHOD[net_type]:

@@ -2370,6 +2370,44 @@ def metrics_msssim_lv(E, Hh, border, levels=255, scales=5, inputs_are_levels=Fal
     return out
 
 
+FRC_MIN_SIDE, FRC_MAX_SIDE = 32, 2048
+FRC_THRESHOLD = 1.0 / 7.0
+
+
+def frc_side(h, w):
+    """the side S of the centred square the Fourier ring correlation transforms: the largest power of two not above min(h, w), at
+    most 2048; 0 when a side is below 32 (the entry point refuses such an image)"""
+    m = min(int(h), int(w))
+    if m < FRC_MIN_SIDE:
+        return 0
+    return min(1 << (m.bit_length() - 1), FRC_MAX_SIDE)
+
+
+def frc_threshold(threshold):
+    """the threshold of the cutoff search: a number in (0, 1)"""
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not 0.0 < threshold < 1.0:
+        raise ValueError(f"frc: the threshold {threshold} is outside (0, 1)")
+    return float(threshold)
+
+
+def metrics_frc_lv(E, Hh, levels=255, threshold=FRC_THRESHOLD, inputs_are_levels=False):
+    """Fourier ring correlation of E against Hh at ``levels`` grey levels in float64 (include/srhip.h states it): the curve, fp64
+    [B, S/2 + 1] over the rings 0 .. S/2 of the centred S x S square (``frc_side``), and the cutoff, fp64 [B], the first crossing
+    of ``threshold`` as a fraction of Nyquist"""
+    _chk(E, Hh)
+    E, Hh = E.float().contiguous(), Hh.float().contiguous()
+    B = E.shape[0]
+    H, W = E.shape[-2:]
+    S = frc_side(H, W)
+    n = max(lib.srhip_metrics_frc_lv_ws(B, H, W), 1)
+    ws = SCRATCH.get("frc_lv_ws", n, torch.float64, E.device)
+    curve = torch.empty(B, S // 2 + 1, dtype=torch.float64, device=E.device)
+    cut = torch.empty(B, dtype=torch.float64, device=E.device)
+    call("srhip_metrics_frc_lv", _p(E), _p(Hh), B, H, W, _levels(levels, "metrics_frc_lv"), int(inputs_are_levels),
+         frc_threshold(threshold), _p(ws), ws.numel(), _p(curve), _p(cut), _st())
+    return curve, cut
+
+
 # ------------------------------------------------------------------ optimizers
 def adam_step(p, g, m, v, step, lr, b1=0.9, b2=0.999, eps=1e-8, wd=0.0, gscale=1.0, skip_flag=None):
     _chk(p, g, m, v, skip_flag)
