@@ -301,7 +301,8 @@ class ResidentTrainSet:
     def __init__(self, args, pairs_h: dict, pairs_l: dict, device, rank: int = 0, world: int = 1):
         import torch
         import torch.nn.functional as F
-        from dlib.utils.utils_dataloaders import imread_gray, check_in_max, refuse_16bit, ShardedSampler
+        from dlib.utils.utils_dataloaders import imread_gray, refuse_16bit, ShardedSampler
+        from dlib.utils.own_options import check_in_max
         from dlib.datasets import lowres
         if getattr(args, 'augment', False):
             raise NotImplementedError("ResidentTrainSet: --augment (the reference drops it too: dataset_dpsr.py:860-862 'passed')")

@@ -84,7 +84,7 @@ from os.path import join
 
 import numpy as np
 
-from dlib.utils import constants
+from dlib.utils import constants, own_options
 
 
 def get_pairs(path_file: str) -> dict:
@@ -143,97 +143,7 @@ def imread_gray(path: str) -> np.ndarray:
                                   f"images")
 
 
-def check_in_max(in_max):
-    """--in_max: the white level of 16-bit tiles, 1 .. 65535 (None: 65535); no effect on 8-bit tiles"""
-    if in_max is None:
-        return 65535
-    if isinstance(in_max, bool) or int(in_max) != in_max or not 1 <= in_max <= 65535:
-        raise ValueError(f'--in_max {in_max}: the white level of 16-bit tiles is an integer in 1 .. 65535')
-    return int(in_max)
-
-
-def check_metric_levels(levels):
-    """--metric_levels: the white level the metrics quantise both images to, 255 .. 65535 (None: 255, the reference's metrics)"""
-    if levels is None:
-        return 255
-    if isinstance(levels, bool) or int(levels) != levels or not 255 <= levels <= 65535:
-        raise ValueError(f'--metric_levels {levels}: the white level of the metrics is an integer in 255 .. 65535')
-    return int(levels)
-
-
-def check_msssim(args):
-    """--msssim / --msssim_scales: the number of scales of the multi-scale SSIM this run computes, 1 .. 5 (default 5), or 0
-    without --msssim True; also what --model_select_mtr msssim needs"""
-    from dlib.utils import constants
-    on, scales = getattr(args, 'msssim', None), getattr(args, 'msssim_scales', None)
-    if not on:
-        if scales is not None:
-            raise ValueError(f'--msssim_scales {scales} needs --msssim True')
-        if getattr(args, 'model_select_mtr', None) == constants.MSSSIM_MTR:
-            raise ValueError(f'--model_select_mtr {constants.MSSSIM_MTR} needs --msssim True')
-        return 0
-    scales = 5 if scales is None else scales
-    if isinstance(scales, bool) or int(scales) != scales or not 1 <= scales <= 5:
-        raise ValueError(f'--msssim_scales {scales}: the number of scales is an integer in 1 .. 5')
-    if getattr(args, 'model_select_mtr', None) == constants.MSSSIM_MTR and getattr(args, 'eval_over_roi_also_model_select', False):
-        raise ValueError(f'--model_select_mtr {constants.MSSSIM_MTR} is a whole-image metric: it cannot select the model over the '
-                         f'ROI (--eval_over_roi_also_model_select True)')
-    return int(scales)
-
-
-def check_frc(args):
-    """--frc / --frc_threshold: the threshold of the Fourier ring correlation cutoff this run reports, a number in (0, 1) (default
-    1 / 7), or 0 without --frc True.  The cutoff is a report metric, a threshold crossing that is discontinuous in the weights:
-    --model_select_mtr frc_cut is refused by name, with or without the option"""
-    from dlib.utils import constants
-    on, thr = getattr(args, 'frc', None), getattr(args, 'frc_threshold', None)
-    if getattr(args, 'model_select_mtr', None) == constants.FRC_CUT:
-        raise ValueError(f'--model_select_mtr {constants.FRC_CUT}: the cutoff of the Fourier ring correlation is a report metric '
-                         f'(--frc True), not a selection criterion')
-    if not on:
-        if thr is not None:
-            raise ValueError(f'--frc_threshold {thr} needs --frc True')
-        return 0
-    thr = 1.0 / 7.0 if thr is None else thr
-    if isinstance(thr, bool) or not isinstance(thr, (int, float)) or not 0.0 < thr < 1.0:
-        raise ValueError(f'--frc_threshold {thr}: the threshold is a number in (0, 1)')
-    return float(thr)
-
-
-LR_SYNTHS = ('bicubic', 'psf')
 LR_SYNTH_EVAL_SALT = 0x6C725F73796E7468        # + item index: the noise seed of a validation / test item under --lr_synth psf
-
-
-def check_lr_synth(args):
-    """--lr_synth (not a reference option): None for 'bicubic' (or no key: util.imresize_np, the reference's LR image of an
-    HR-only pair), else (sigma, photons, read_std) of the camera model 'psf' -- clean = bin_s(G_sigma * HR), LR = (Poisson(photons
-    * clean) + read_std * N(0, 1)) / photons; photons 0: no noise.  A value the kernels cannot run is refused by option name."""
-    from dlib.datasets import lowres
-    kind = getattr(args, 'lr_synth', None)
-    if kind is None:
-        kind = 'bicubic'
-    if kind not in LR_SYNTHS:
-        raise ValueError(f"--lr_synth {kind}: one of {', '.join(LR_SYNTHS)}")
-    vals = {}
-    for k in ('lr_synth_psf_sigma', 'lr_synth_photons', 'lr_synth_read_std'):
-        v = getattr(args, k, None)
-        v = 0. if v is None else v
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0. <= v < math.inf:
-            raise ValueError(f"--{k} {v}: a finite number >= 0")
-        vals[k] = float(v)
-    sigma, photons, read_std = vals['lr_synth_psf_sigma'], vals['lr_synth_photons'], vals['lr_synth_read_std']
-    if kind != 'psf':
-        if sigma or photons or read_std:
-            raise ValueError("--lr_synth_psf_sigma / --lr_synth_photons / --lr_synth_read_std need --lr_synth psf")
-        return None
-    if int(4.0 * sigma + 0.5) > lowres.LR_BLUR_MAX_RADIUS:
-        raise ValueError(f"--lr_synth_psf_sigma {sigma} gives a blur radius of {int(4.0 * sigma + 0.5)}, above "
-                         f"{lowres.LR_BLUR_MAX_RADIUS}")
-    if photons > lowres.LR_SYNTH_MAX_PHOTONS:
-        raise ValueError(f"--lr_synth_photons {photons}: at most {lowres.LR_SYNTH_MAX_PHOTONS:g}")
-    if read_std > 0. and photons == 0.:
-        raise ValueError(f"--lr_synth_read_std {read_std} needs --lr_synth_photons above 0: the read noise is in photon counts")
-    return sigma, photons, read_std
 
 
 def refuse_16bit(args, tile):
@@ -256,7 +166,7 @@ def unit_of_levels(img: np.ndarray, in_max=None) -> np.ndarray:
     if img.dtype == np.uint8:
         return np.float32(img / 255.)
     assert img.dtype == np.uint16, img.dtype
-    m = check_in_max(in_max)
+    m = own_options.check_in_max(in_max)
     return np.float32(np.minimum(img, m) / float(m))
 
 
@@ -285,8 +195,8 @@ class EvalPairs:
         self.args, self.pairs_h, self.pairs_l = args, pairs_h, pairs_l
         self.im_h_ids = list(pairs_h.keys())
         self.sf = args.scale
-        self.in_max = check_in_max(getattr(args, 'in_max', None))       # the white level of 16-bit tiles (--in_max)
-        self.lr_synth = check_lr_synth(args)        # None: bicubic; (sigma, photons, read_std): the camera model (--lr_synth psf)
+        self.in_max = own_options.check_in_max(getattr(args, 'in_max', None))       # the white level of 16-bit tiles (--in_max)
+        self.lr_synth = own_options.check_lr_synth(args)        # None: bicubic; (sigma, photons, read_std): the camera model (--lr_synth psf)
         self._psf_weights = None
         # ids <-> floats (dataset_dpsr.py:583-590): per-image details travel through all_gather as floats
         self.im_h_ids_to_float = {k: float(i) for i, k in enumerate(self.im_h_ids)}

@@ -31,7 +31,8 @@ def _fresh_metrics(extra=()) -> dict:
 def extra_metrics(args, roi: bool = False) -> list:
     """the metrics beyond constants.METRICS that this run computes: 'msssim' under --msssim True, a whole-image metric that the
     ROI tracker never holds.  Without the option: none, and the trackers keep the reference's keys."""
-    return [constants.MSSSIM_MTR] if getattr(args, 'msssim', None) and not roi else []
+    from dlib.utils.own_options import eval_plan
+    return [constants.MSSSIM_MTR] if eval_plan(args).msssim_scales and not roi else []
 
 
 def _scalar(v):

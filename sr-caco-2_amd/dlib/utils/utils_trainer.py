@@ -199,19 +199,12 @@ def fast_eval(model, data_loader, ds_name: str, split: str, tracker: dict, roi_t
         reset_tracker_eval(roi_tracker, split, ds_name)
     model.set_eval_mode()
     border = args.scale
-    from dlib.utils.utils_dataloaders import check_metric_levels, check_msssim, check_frc
+    from dlib.utils.own_options import eval_plan
     from srhip.ops import FRC_MIN_SIDE
-    # --metric_levels: the sweep at another white level; not given, today's call
-    sweep_opts = {} if check_metric_levels(getattr(args, 'metric_levels', None)) == 255 else {'levels': int(args.metric_levels)}
-    # --msssim True: the sweep adds the multi-scale SSIM, a whole-image metric (no ROI slots); not given, today's call and keys
-    n_scales = check_msssim(args)
-    if n_scales:
-        sweep_opts['msssim'] = n_scales
+    # the options beyond the reference's (own_options.OPTIONS), resolved once; none given: the reference's calls and keys
+    plan = eval_plan(args)
+    sweep_opts, frc_opts, n_scales, frc_thr = plan.sweep_kwargs(), plan.frc_kwargs(), plan.msssim_scales, plan.frc_threshold
     mtrs = _MTRS + ((constants.MSSSIM_MTR,) if n_scales else ())
-    # --frc True: one more call a batch, the Fourier ring correlation of the whole image.  A report metric: per-image cutoffs in
-    # the details, the mean in the log, never in a tracker; not given, today's calls and keys
-    frc_thr = check_frc(args)
-    frc_opts = {} if 'levels' not in sweep_opts else {'levels': sweep_opts['levels']}
     frc_sum, frc_curves = 0.0, {}                           # sum of cutoffs; side -> [sum of curves, images]
     with_roi = bool(args.eval_over_roi_also)
     ths = tuple(int(t) for t in args.eval_over_roi_also_ths) if with_roi else ()

@@ -31,21 +31,13 @@ if HERE not in sys.path:
 import yaml  # noqa: E402
 import torch  # noqa: E402
 
-from dlib.utils import constants  # noqa: E402
+from dlib.utils import constants, own_options  # noqa: E402
 import dlib.dllogger as DLLogger  # noqa: E402
 from dlib.utils.tools import Dict2Obj  # noqa: E402
 from dlib.models.select_model import define_model  # noqa: E402
-from dlib.utils.utils_dataloaders import get_all_eval_loaders, check_msssim, check_frc  # noqa: E402
+from dlib.utils.utils_dataloaders import get_all_eval_loaders  # noqa: E402
 from dlib.utils.utils_trainer import evaluate  # noqa: E402
 from dlib.utils.utils_tracker import find_last_tracker, save_tracker  # noqa: E402
-
-
-def str2bool(v):
-    if v.lower() in ('true', '1', 'yes'):
-        return True
-    if v.lower() in ('false', '0', 'no'):
-        return False
-    raise argparse.ArgumentTypeError(f'boolean expected, got {v!r}')
 
 
 def load_args(argv=None):
@@ -60,49 +52,14 @@ def load_args(argv=None):
                          "3 x8 self-ensemble, 4 split and x8")
     ap.add_argument("--test_refield", type=int, default=32, help="--test_mode 2 / 4: receptive field of the net")
     ap.add_argument("--test_min_size", type=int, default=256, help="--test_mode 2 / 4: up to min_size^2 pixels go in whole")
-    ap.add_argument("--in_max", type=int, default=None,
-                    help="white level of 16-bit tiles, 1 .. 65535 (default: the one the run recorded in config_model.yml, "
-                         "else 65535); no effect on 8-bit tiles")
-    ap.add_argument("--metric_levels", type=int, default=None,
-                    help="white level the metrics quantise prediction and target to, 255 .. 65535 (default: the one the run "
-                         "recorded in config_model.yml, else 255: the reference's 8-bit-level metrics); the bicubic baseline "
-                         "row is measured at the same level")
-    ap.add_argument("--msssim", type=str2bool, default=None,
-                    help="also compute the multi-scale SSIM (Wang, Simoncelli, Bovik 2003) of the net and of the bicubic baseline "
-                         "row (default: what the run recorded in config_model.yml, else off)")
-    ap.add_argument("--msssim_scales", type=int, default=None,
-                    help="--msssim True: the number of scales, 1 .. 5 (default: the run's, else 5); both sides of an evaluation "
-                         "image, the border excluded, must be at least 10 * 2^(scales - 1) + 1")
-    ap.add_argument("--frc", type=str2bool, default=None,
-                    help="also compute the Fourier ring correlation of prediction against target, for the net and for the bicubic "
-                         "baseline row: 'frc_cut' per image in details_*.yml, best-models/frc_<ds>.yml, the mean in the log "
-                         "(default: what the run recorded in config_model.yml, else off)")
-    ap.add_argument("--frc_threshold", type=float, default=None,
-                    help="--frc True: the threshold of the cutoff, in (0, 1) (default: the run's, else 1 / 7)")
+    own_options.add_arguments(ap, "eval")
     ns = ap.parse_args(argv)
-    if ns.in_max is not None and not 1 <= ns.in_max <= 65535:
-        ap.error(f"--in_max {ns.in_max}: the white level of 16-bit tiles is an integer in 1 .. 65535")
-    if ns.metric_levels is not None and not 255 <= ns.metric_levels <= 65535:
-        ap.error(f"--metric_levels {ns.metric_levels}: the white level of the metrics is an integer in 255 .. 65535")
     exp_path = ns.exp_path
     assert exp_path and isdir(exp_path), exp_path
     with open(join(exp_path, 'config_model.yml'), 'r') as fy:
         args = Dict2Obj(yaml.safe_load(fy))
     args.distributed = False
-    if ns.in_max is not None:
-        args.in_max = ns.in_max
-    if ns.metric_levels is not None:
-        args.metric_levels = ns.metric_levels
-    for k in ('msssim', 'msssim_scales', 'frc', 'frc_threshold'):
-        if getattr(ns, k) is not None:
-            args[k] = getattr(ns, k)
-    if ns.frc is False and ns.frc_threshold is None:
-        args.pop('frc_threshold', None)               # --frc False alone turns off a run recorded with a threshold of its own
-    try:
-        check_msssim(args)
-        check_frc(args)
-    except ValueError as e:
-        ap.error(str(e))
+    own_options.apply_recorded(args, ns, ap.error)
     if ns.data_root is None:
         raise SystemExit("eval.py: give --data_root (or SRHIP_DATA_ROOT): the parent of the dataset folders")
     args.data_root = ns.data_root

@@ -40,19 +40,11 @@ if HERE not in sys.path:
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
-from dlib.utils import constants  # noqa: E402
+from dlib.utils import constants, own_options  # noqa: E402
+from dlib.utils.own_options import str2bool  # noqa: E402
 from dlib.utils.shared import safe_str_var  # noqa: E402
+from dlib.utils.tools import Dict2Obj  # noqa: E402
 from dlib.utils.utils_init_default_args import init_net_g  # noqa: E402
-
-
-def str2bool(v):
-    if isinstance(v, bool):
-        return v
-    if v.lower() in ('true', '1', 'yes'):
-        return True
-    if v.lower() in ('false', '0', 'no'):
-        return False
-    raise argparse.ArgumentTypeError(f'boolean expected, got {v!r}')
 
 
 def plus_list(v):
@@ -65,13 +57,6 @@ def int_or_float(v):
         return int(v)
     except ValueError:
         return float(v)
-
-
-class Dict2Obj(dict):
-    __getattr__ = dict.get
-
-    def __setattr__(self, k, v):
-        self[k] = v
 
 
 def get_config(net_type):
@@ -177,37 +162,7 @@ def parse_input(argv=None):
               'da_dot_bin_noise_prob', 'da_dot_bin_noise_area', 'da_dot_bin_noise_p', 'da_add_gaus_noise_prob',
               'da_add_gaus_noise_area', 'da_add_gaus_noise_std'):
         ap.add_argument(f'--{k}', type=float, default=None)
-    # (not a reference option) the white level of 16-bit tiles, which are read as min(v, in_max) / in_max: 65535 when not
-    # given, 4095 for 12-bit data in a 16-bit container; no effect on 8-bit tiles.  A key of the configuration -- and of
-    # config_model.yml, where eval.py and predict.py find it -- only when given.
-    ap.add_argument('--in_max', type=int, default=None)
-    # (not a reference option) the white level the evaluation metrics quantise prediction and target to, 255 .. 65535 --
-    # normally the set's in_max.  Not given: 255, the reference's 8-bit-level metrics.  Given: MSE in levels^2, PSNR against
-    # that white level, SSIM in float64 (dlib.metrics.sweep); the ROIs stay defined at the 8-bit levels.  A key of the
-    # configuration and of config_model.yml -- where eval.py finds it, and a resumed run checks it -- only when given.
-    ap.add_argument('--metric_levels', type=int, default=None)
-    # (not reference options) --msssim True: every evaluation also computes the multi-scale SSIM of Wang, Simoncelli and Bovik
-    # (2003) over --msssim_scales scales (1 .. 5, default 5), in float64 at the white level of the metrics (include/srhip.h states
-    # it): 'msssim' in the tracker, details_*.yml, the best-model yaml files and the log, never in the ROI files; and
-    # --model_select_mtr msssim becomes possible.  Keys of the configuration and of config_model.yml -- where eval.py finds them,
-    # and a resumed run checks them -- only when given.
-    ap.add_argument('--msssim', type=str2bool, default=None)
-    ap.add_argument('--msssim_scales', type=int, default=None)
-    # (not reference options) --frc True: every evaluation also computes the Fourier ring correlation of prediction against target
-    # (include/srhip.h states it) and reports its cutoff at --frc_threshold (in (0, 1), default 1 / 7) as a fraction of Nyquist:
-    # 'frc_cut' per image in details_*.yml, the set mean in the log, best-models/frc_<ds>.yml with the mean curve.  A report
-    # metric: no tracker holds it and --model_select_mtr frc_cut is refused.  Keys of the configuration and of config_model.yml
-    # -- where eval.py finds them -- only when given; nothing a resumed run records depends on them.
-    ap.add_argument('--frc', type=str2bool, default=None)
-    ap.add_argument('--frc_threshold', type=float, default=None)
-    # (not a reference option) how the LR image of an HR-only pair is made: 'bicubic' (default: util.imresize_np, the
-    # reference's) or 'psf', a camera model -- clean = bin_s(G_sigma * HR) with sigma in HR pixels, then per training batch
-    # LR = (Poisson(photons * clean) + read_std * N(0, 1)) / photons with photons the expected count at white level and read_std
-    # in counts; photons 0: no noise.  float32, no offset, no clipping, no quantisation.  Keys of the configuration and of
-    # config_model.yml -- where eval.py finds them -- only when --lr_synth is given.
-    ap.add_argument('--lr_synth', type=str, default=None)
-    for k in ('lr_synth_psf_sigma', 'lr_synth_photons', 'lr_synth_read_std'):
-        ap.add_argument(f'--{k}', type=float, default=None)
+    own_options.add_arguments(ap, 'main')                                    # the options the reference does not have
     ap.add_argument('--init_pretrained_path', type=str, default=None)        # netG['init_pretrained_path'] (utils_config.py:146)
     for k, t in IGNORED_FLAGS.items():
         if k not in cfg['train']:
@@ -264,24 +219,6 @@ def parse_input(argv=None):
         if v is not None and dflt is not None and v != dflt:
             ap.error(f"--{k} {v}: this option changes what the run computes and is not implemented on this path "
                      f"(only the reference's default {dflt!r} is accepted)")
-    if ns.in_max is not None and not 1 <= ns.in_max <= 65535:
-        ap.error(f"--in_max {ns.in_max}: the white level of 16-bit tiles is an integer in 1 .. 65535")
-    if ns.metric_levels is not None and not 255 <= ns.metric_levels <= 65535:
-        ap.error(f"--metric_levels {ns.metric_levels}: the white level of the metrics is an integer in 255 .. 65535")
-    synth_keys = ('lr_synth_psf_sigma', 'lr_synth_photons', 'lr_synth_read_std')
-    if ns.lr_synth is None:
-        given = [k for k in synth_keys if getattr(ns, k) is not None]
-        if given:
-            ap.error(f"--{given[0]} needs --lr_synth psf")
-    else:
-        from dlib.utils.utils_dataloaders import check_lr_synth
-        for k in synth_keys:
-            if getattr(ns, k) is None:
-                setattr(ns, k, 0.)
-        try:
-            check_lr_synth(ns)
-        except ValueError as e:
-            ap.error(str(e))
     # any non-None CLI value overrides the top-level / nested key (utils_parser.py:900-923)
     skip = set(IGNORED_FLAGS) | set(DEFAULT_ONLY_FLAGS) | {f'{nt}_{k}' for k in init_defaults} | {'init_pretrained_path'}
     for k, v in vars(ns).items():
@@ -291,12 +228,8 @@ def parse_input(argv=None):
             cfg['train'][k] = v
         elif not k.startswith(nt + '_'):
             cfg[k] = v
-    from dlib.utils.utils_dataloaders import check_msssim, check_frc
-    try:
-        check_msssim(Dict2Obj(cfg))
-        check_frc(Dict2Obj(cfg))
-    except ValueError as e:
-        ap.error(str(e))
+    cfg = Dict2Obj(cfg)
+    own_options.validate(cfg, ap.error)
     if cfg['method'] != constants.NETTYPE_METHOD[net_type]:
         raise ValueError(f"--method {cfg['method']} does not match --net_type {net_type} "
                          f"({constants.NETTYPE_METHOD[net_type]})")
@@ -309,7 +242,7 @@ def parse_input(argv=None):
         v = getattr(ns, f'{nt}_{k}')
         if v is not None:
             cfg['netG'][f'{nt}_{k}'] = v
-    return Dict2Obj(cfg)
+    return cfg
 
 
 def synth_batch(batch, scale, h_size, device, seed):
@@ -345,20 +278,16 @@ def _resume_point(args):
         except Exception:                       # python-tagged values the safe loader refuses: compare the text
             old = {}
             txt = open(cfg_path).read()
-            for key in ('net_type', 'scale', 'metric_levels', 'msssim', 'msssim_scales'):
+            for key in ('net_type', 'scale') + own_options.RESUME_KEYS:
                 import re
                 m = re.search(rf'^{key}:\s*(\S+)', txt, re.M)
                 if m:
                     old[key] = m.group(1)
         if 'net_type' not in old and isinstance(old.get('netG'), dict) and 'net_type' in old['netG']:
             old['net_type'] = old['netG']['net_type']           # (the reference's own files keep it under netG)
-        # metric_levels, absent meaning 255: a tracker that mixed 8-bit and full-depth PSNRs would select a wrong best model
-        old.setdefault('metric_levels', 255)
-        # msssim_scales, 0 meaning a run without --msssim True: its tracker would gain or lose the key
-        from dlib.utils.utils_dataloaders import check_msssim
-        old['msssim_scales'] = int(old.get('msssim_scales') or 5) if str(old.pop('msssim', None)).lower() == 'true' else 0
-        asked = {'net_type': args.net_type, 'scale': args.scale, 'metric_levels': getattr(args, 'metric_levels', None) or 255,
-                 'msssim_scales': check_msssim(args)}
+        # what else a resumed run must match (own_options.GROUPS): there an absent key means the option's default
+        old.update({r.key: r.recorded(old) for r in own_options.RESUME})
+        asked = {'net_type': args.net_type, 'scale': args.scale, **{r.key: r.asked(args) for r in own_options.RESUME}}
         for key, want in asked.items():
             if key in old and str(old[key]) != str(want):
                 raise SystemExit(f"--outd {args.outd_backup} holds an experiment with {key} = {old[key]} (config_model.yml); this "
@@ -476,10 +405,9 @@ def main(argv=None):
     model = _forward_with_padding(batch, model, args)          # SwinIR: flipped-strip padding to the next window multiple
     vis = model.current_visuals()
     ths = tuple(args.eval_over_roi_also_ths) if args.eval_over_roi_also else ()
-    from dlib.utils.utils_dataloaders import check_msssim
-    n_scales = check_msssim(args)
-    sw = metrics.sweep(vis['E'], vis['H'], border=args.scale, thresholds=ths, levels=args.metric_levels or 255,
-                       **({'msssim': n_scales} if n_scales else {}))
+    plan = own_options.eval_plan(args)
+    n_scales = plan.msssim_scales
+    sw = metrics.sweep(vis['E'], vis['H'], border=args.scale, thresholds=ths, **plan.sweep_kwargs())
     if rank == 0:
         for k in (constants.PSNR_MTR, constants.PSNR_Y_MTR, constants.MSE_MTR, constants.NRMSE_MTR,
                   constants.SSIM_MTR):

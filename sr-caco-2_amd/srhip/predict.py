@@ -21,6 +21,7 @@ from os.path import join
 import numpy as np
 
 from dlib.utils import constants
+from dlib.utils.own_options import in_levels
 
 OUT_DTYPES = ("same", "uint8", "uint16", "float32")
 _RANGE = {"uint8": 255, "uint16": 65535}
@@ -80,7 +81,7 @@ def check_request(args, dtype, H, W, in_max=None, out_dtype="same"):
         in_max = getattr(args, "in_max", None)
     if in_max is None:
         in_max = _RANGE[name]
-    if int(in_max) != in_max or not 1 <= in_max <= _RANGE[name]:
+    if not in_levels(in_max, 1, _RANGE[name]):
         raise PredictError(f"in_max {in_max} is outside 1 .. {_RANGE[name]}, the range of {name} pages")
     if net == constants.SRCNN and in_max != 255:
         raise PredictError("SRCNN reads the interpolated uint8 image / 255: in_max does not apply to it")
@@ -98,7 +99,7 @@ class Predictor:
                  out_dtype="same"):
         if out_dtype not in OUT_DTYPES:
             raise PredictError(f"out_dtype must be one of {OUT_DTYPES} (got {out_dtype!r})")
-        if in_max is not None and (int(in_max) != in_max or not 1 <= in_max <= 65535):
+        if in_max is not None and not in_levels(in_max, 1, _RANGE["uint16"]):
             raise PredictError(f"in_max {in_max} is outside 1 .. 65535, the range of uint16 pages")
         if int(test_mode) not in range(5):
             raise PredictError(f"test_mode 0 .. 4 (got {test_mode})")

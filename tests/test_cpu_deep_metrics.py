@@ -149,7 +149,7 @@ def test_a_run_does_not_resume_a_folder_with_other_metric_levels(tmp_path):
 
 
 def test_check_metric_levels():
-    from dlib.utils.utils_dataloaders import check_metric_levels
+    from dlib.utils.own_options import check_metric_levels
     assert check_metric_levels(None) == 255 and check_metric_levels(255) == 255 and check_metric_levels(65535) == 65535
     for bad in (254, 65536, 4095.5, True):
         with pytest.raises(ValueError, match="255 .. 65535"):

@@ -161,7 +161,7 @@ def _main(*flags):
 
 
 def test_main_cli_accepts():
-    from dlib.utils.utils_dataloaders import check_frc
+    from dlib.utils.own_options import check_frc
     for flags in ((), ("--frc", "False")):
         a = _main(*flags)
         assert "frc_threshold" not in a and not a.frc and ("frc" in a) == bool(flags) and check_frc(a) == 0
@@ -217,7 +217,7 @@ def test_eval_frc_false_turns_off_a_recorded_run(tmp_path, capsys):
     off (the inherited threshold goes with it); --frc False with a threshold given on the command line is still refused"""
     import shutil
     import yaml
-    from dlib.utils.utils_dataloaders import check_frc
+    from dlib.utils.own_options import check_frc
     exp = tmp_path / "exp"
     os.makedirs(exp)
     cfg = yaml.safe_load(open(os.path.join(FX, "exp", "config_model.yml")))

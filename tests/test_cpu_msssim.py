@@ -129,7 +129,7 @@ def test_main_cli_accepts():
     assert a.msssim is True and a.msssim_scales == 3 and a.model_select_mtr == "msssim"
     a = _main("--msssim", "True", "--model_select_mtr", MSSSIM_MTR, "--eval_over_roi_also", "True")
     assert a.eval_over_roi_also and not a.eval_over_roi_also_model_select
-    from dlib.utils.utils_dataloaders import check_msssim
+    from dlib.utils.own_options import check_msssim
     assert check_msssim(_main()) == 0 and check_msssim(_main("--msssim", "True")) == 5
     assert check_msssim(_main("--msssim", "True", "--msssim_scales", "1")) == 1
 

@@ -128,7 +128,7 @@ def test_main_parses_lr_synth_and_config_model_has_the_keys_only_when_given(tmp_
     import yaml
     import main as M
     from dlib.utils.utils_config import save_config
-    from dlib.utils.utils_dataloaders import check_lr_synth
+    from dlib.utils.own_options import check_lr_synth
     plain = M.parse_input(BASE)
     assert all(k not in dict(plain) for k in KEYS) and check_lr_synth(plain) is None
     cfg = M.parse_input(BASE + PSF)
@@ -178,7 +178,8 @@ def _caco2_args(**kw):
 
 
 def test_a_set_without_an_hr_only_pair_refuses_lr_synth_psf():
-    from dlib.utils.utils_dataloaders import get_train_set, check_lr_synth
+    from dlib.utils.utils_dataloaders import get_train_set
+    from dlib.utils.own_options import check_lr_synth
     with pytest.raises(ValueError, match="--lr_synth psf: the set has no HR-only pair"):
         get_train_set(_caco2_args(lr_synth="psf", lr_synth_psf_sigma=1.2, lr_synth_photons=150.0), "cpu")
     # the same values are refused by name when a set is built from a configuration that never saw the parser
