@@ -1012,6 +1012,45 @@ int srhip_metrics_msssim_lv(const float* E, const float* Hh, int B, int H, int W
 long srhip_metrics_frc_lv_ws(int B, int H, int W);
 int srhip_metrics_frc_lv(const float* E, const float* Hh, int B, int H, int W, int L, int inputs_are_levels, double threshold,
                          double* workspace, long workspace_doubles, double* curve, double* cut, void* stream);
+/* Image decorrelation analysis (predict.py --resolution; Descloux, Grussmayer, Radenovic, Nature Methods 2019): the resolution of
+ * each image of a [B][H][W] single-channel batch at L levels from that image alone, with no second image and no target,
+ * float64.  This text is the definition:
+ *   1. levels: Q_L (skipped if inputs_are_levels), x = level / L in float64;
+ *   2. square: the centred S x S square of srhip_metrics_frc_lv (S the largest power of two not above min(H, W), at most 2048,
+ *      offsets (H - S) / 2 and (W - S) / 2); NO border crop; S < 32 is refused;
+ *   3. window and transform: the separable periodic Hann window of the FRC, then ONE unnormalised FFT2, F;
+ *   4. NO mean subtraction: the window's own spectrum lives on kx, ky in {0, +-1}, exactly the rings 0 and 1 of the FRC's integer
+ *      ring rule, so every sum below runs over the rings q = 2 .. S/2 only, which removes the pedestal exactly;
+ *   5. ring statistics, rings (2q - 1)^2 <= 4 |k|^2 < (2q + 1)^2 as in the FRC: A_q = sum |F|, Q_q = sum |F|^2 over the ring,
+ *      n_q = the number of frequencies on it (an integer);
+ *   6. decorrelation curves: a high-pass of width sigma (pixels) is radial and taken as constant on a ring,
+ *      g_sigma(q) = -expm1(-2 pi^2 sigma^2 q^2 / S^2), and g = 1 without a filter;
+ *        d_sigma(r) = sum_{q=2..r} g(q) A_q / sqrt((sum_{q=2..S/2} g(q)^2 Q_q) * sum_{q=2..r} n_q),  r = 2 .. S/2,
+ *      0 where the product under the root is not positive, and d(0) = d(1) = 0.  This is Descloux's d(r), the correlation of
+ *      the filtered spectrum with its own normalised copy F / |F| inside the disk of radius r: only |F| survives in the
+ *      numerator.  The filter is applied in frequency, not as image minus blurred image;
+ *   7. peak of a curve: start with m = S/2 and repeat: i = the FIRST argmax of d[2 .. m]; if i == 2 there is no peak (ring 0,
+ *      amplitude 0); if i == m, m <- m - 1; else if d[i] - min(d[i .. m]) >= 5e-4 the peak is (i, d[i]); else m <- m - 1;
+ *   8. filter banks: curve 0 is unfiltered, its peak ring is q0.  sigma_max = S / q0 (S / 2 if q0 = 0), sigma_min = 0.15; bank 1 is
+ *      sigma_j = exp(linspace(ln sigma_max, ln sigma_min, 10)[j - 1]), j = 1 .. 10 (start + k * step, the stop itself at the
+ *      end).  The best of the curves 0 .. 10 is the one with the largest peak ring, the lowest index among equals.  If it is
+ *      j >= 1, bank 2 (curves 11 .. 20) is ten more widths by the same rule from sigma_max(j - 1, 1) down to sigma_min(j + 1, 10);
+ *      if it is curve 0 there is no bank 2: curves 11 .. 20 are all 0 and report ring 0.  The result is the best of all 21;
+ *   9. per image out[b][5] = cut, ring, amp, sigma, side: ring the best curve's peak ring, cut = ring / (S/2) a fraction of
+ *      Nyquist (2 / cut is the resolution in pixels; cut = 0: no resolution was found), amp the peak's height (an indicator of the
+ *      signal-to-noise ratio), sigma the best curve's width (0 for curve 0), side = S.
+ * curves[b][21][S/2 + 1] and peaks[b][21] (the peak rings, int) are written when the pointers are not NULL.
+ * How this departs from Descloux's ImageJ / MATLAB code: a Hann window instead of a cosine apodisation of the edge and no mean
+ * subtraction (4.); the integer rings of the FRC instead of 50 sampled radii; filters constant on a ring; no refinement of the
+ * radius after the second bank.  A figure from this code is comparable with another figure from this code.
+ * Two images share one complex transform (z = win x_a + i win x_b; an odd B ends with a zero partner), radix-2 in LDS; every
+ * sum is taken in a fixed order and nothing is accumulated with atomics: two calls give the same bits.  Three launches, no host
+ * synchronisation, no allocation.
+ * workspace doubles: srhip_metrics_decorr_lv_ws(B, H, W) (0: a side is below 32); workspace_doubles is what the caller's buffer
+ * holds, and a shorter one is refused; the workspace is 16-byte aligned. */
+long srhip_metrics_decorr_lv_ws(int B, int H, int W);
+int srhip_metrics_decorr_lv(const float* img, int B, int H, int W, int L, int inputs_are_levels, double* workspace,
+                            long workspace_doubles, double* out, double* curves, int* peaks, void* stream);
 
 /* Weight (and bias) gradients of up to 40 3x3 convolutions of ONE shape -- the body of an
  * EDSR-style stack (network_nlsn.py:72-93,325-345 backward) -- in one contraction launch plus one

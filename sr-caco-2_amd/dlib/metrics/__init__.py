@@ -23,6 +23,10 @@ white level, a whole-image metric without ROI slots, and needs both cropped side
 target and its cutoff, the resolution figure of the light-microscopy literature; include/srhip.h (srhip_metrics_frc_lv) states it.
 A call of its own, never part of ``sweep``: a report metric, not a tracker metric.  No border crop (a Hann window instead), the
 centred power-of-two square, float64; both sides at least 32.
+
+``decorr`` (not a reference function; ``predict.py --resolution``): image decorrelation analysis (Descloux, Grussmayer, Radenovic
+2019), the resolution of ONE image with no target and no second acquisition; include/srhip.h (srhip_metrics_decorr_lv) states it.
+The square, the window and the rings are the FRC's; a call of its own, never part of ``sweep``.
 """
 import torch
 
@@ -30,7 +34,7 @@ from srhip import ops
 
 __all__ = ['tensor2uint82float', 'tensor2levels', 'mbatch_gpu_calculate_psnr', 'mbatch_gpu_calculate_mse',
            'mbatch_gpu_calculate_nrmse', 'mbatch_gpu_calculate_ssim', 'mbatch_gpu_calculate_msssim', 'sweep',
-           'frc', 'mbatch_gpu_calculate_frc']
+           'frc', 'mbatch_gpu_calculate_frc', 'decorr']
 
 
 def _need_cuda(t):
@@ -140,3 +144,20 @@ def mbatch_gpu_calculate_frc(x, y, levels=255, threshold=ops.FRC_THRESHOLD):
     _need_cuda(x)
     assert x.ndim == 4 and x.shape == y.shape and x.shape[1] == 1, "1-channel images"
     return ops.metrics_frc_lv(x, y, levels, threshold, True)[1]
+
+
+def decorr(X, levels=255, inputs_are_levels=False, curves=False):
+    """(not a reference function) image decorrelation analysis of every image of X, (B,1,h,w) in [0,1] (or, with
+    ``inputs_are_levels``, floats that hold the levels 0 .. ``levels``): no target is needed.  Returns {'cut': (B,) float64, the
+    resolution as a fraction of Nyquist (2 / cut is the resolution in pixels; 0: none was found), 'ring': (B,) int64, 'amp': (B,)
+    float64, the height of the peak, 'sigma': (B,) float64, the width of the high-pass that gave it (0: none), 'side': S}; with
+    ``curves`` also 'curves': (B, 21, S/2 + 1) float64 and 'peaks': (B, 21) int32, the peak ring of every curve."""
+    _need_cuda(X)
+    assert X.ndim == 4 and X.shape[1] == 1, "1-channel images"
+    res = ops.metrics_decorr_lv(X, levels, inputs_are_levels, curves)
+    out = res[0] if curves else res
+    d = {"cut": out[:, 0].contiguous(), "ring": out[:, 1].to(torch.int64), "amp": out[:, 2].contiguous(),
+         "sigma": out[:, 3].contiguous(), "side": ops.frc_side(*X.shape[-2:])}
+    if curves:
+        d["curves"], d["peaks"] = res[1], res[2]
+    return d

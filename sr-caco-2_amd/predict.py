@@ -3,7 +3,7 @@
 
     python predict.py --exp_path <folder> --input <file | directory> [--output <directory>]
                       [--cudaid 0] [--batch 8] [--in_max N] [--out_dtype same|uint8|uint16|float32]
-                      [--test_mode {0..4} [--test_refield 32] [--test_min_size 256]]
+                      [--test_mode {0..4} [--test_refield 32] [--test_min_size 256]] [--resolution True]
 
 <folder> is the experiment directory ``eval.py`` reads (``config_model.yml``, ``best-models/G-model.pth``).  Inputs are
 single-channel ``.tif`` / ``.tiff`` / ``.png`` files of PIL mode ``L`` or ``I;16`` (a grey palette counts as ``L``); every
@@ -14,7 +14,14 @@ go through the net together, at most ``--batch`` at a time (srhip/predict.py: Pr
 file ``<stem>_x<scale><ext>`` under ``--output`` (default ``<folder>/predict/<basename of the input>/``): same container,
 page count and page order; ``--out_dtype float32`` is written as TIFF mode ``F``.  One log line per file (``log.txt`` /
 ``log.json`` in the output directory).  A file whose pages gave a non-finite output is not written and is named in the
-log; the run goes on with the next file and exits with status 1."""
+log; the run goes on with the next file and exits with status 1.
+
+``--resolution True`` (default off) also measures what the net bought: image decorrelation analysis (Descloux et al. 2019;
+include/srhip.h: srhip_metrics_decorr_lv), a resolution figure from one image with no target, of every LR page and of its
+output.  ``<output>/resolution.yml`` then holds ``{file: [{page, in: {side, cut, res_px, amp}, out: {...}, gain}]}``: ``cut`` a
+fraction of Nyquist, ``res_px = 2 / cut`` in that image's own pixels (null: none found), ``gain = res_px_in * scale /
+res_px_out``; one more log line per file carries the means.  The output files are those of a run without the option.  Every
+page needs both sides to be at least 32."""
 import argparse
 import os
 import sys
@@ -28,6 +35,7 @@ if HERE not in sys.path:
 import numpy as np  # noqa: E402
 
 import dlib.dllogger as DLLogger  # noqa: E402
+from dlib.utils.own_options import str2bool  # noqa: E402
 from srhip.predict import Predictor, PredictError, NonFiniteError, OUT_DTYPES, check_request  # noqa: E402
 
 EXTS = (".tif", ".tiff", ".png")
@@ -127,6 +135,34 @@ def write_pages(path, pages):
         ims[0].save(path)
 
 
+def resolution_rows(records):
+    """{page index: resolution_record} of one file -> its list in resolution.yml, [{page, in, out, gain}] in page order"""
+    return [{"page": k, **records[k]} for k in sorted(records)]
+
+
+def resolution_means(rows):
+    """(mean res_px of the inputs, of the outputs, mean gain) over the pages that have one; None where no page has"""
+    def mean(vals):
+        vals = [v for v in vals if v is not None]
+        return sum(vals) / len(vals) if vals else None
+    return mean(r["in"]["res_px"] for r in rows), mean(r["out"]["res_px"] for r in rows), mean(r["gain"] for r in rows)
+
+
+def resolution_line(name, rows):
+    """the log line of one file under --resolution True"""
+    def px(v):
+        return "none found" if v is None else f"{v:.2f} px"
+    m_in, m_out, gain = resolution_means(rows)
+    return (f"{name}: resolution {px(m_in)} in -> {px(m_out)} out [MEAN of 2 / cut over {len(rows)} page(s), own pixels]"
+            + ("" if gain is None else f", gain x{gain:.2f}"))
+
+
+def write_resolution(out_dir, report):
+    import yaml
+    with open(join(out_dir, "resolution.yml"), "w") as f:
+        yaml.safe_dump(report, f, sort_keys=False)
+
+
 def predict(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--exp_path", type=str, required=True)
@@ -140,6 +176,8 @@ def predict(argv=None):
                     help="0 plain (default), 1 pad, 2 split, 3 x8 self-ensemble, 4 split and x8")
     ap.add_argument("--test_refield", type=int, default=32)
     ap.add_argument("--test_min_size", type=int, default=256)
+    ap.add_argument("--resolution", type=str2bool, default=False,
+                    help="also write resolution.yml: the decorrelation-analysis resolution of every LR page and of its output")
     ns = ap.parse_args(argv)
     pred = Predictor(ns.exp_path, cudaid=ns.cudaid, test_mode=ns.test_mode, test_refield=ns.test_refield,
                      test_min_size=ns.test_min_size, batch=ns.batch, in_max=ns.in_max, out_dtype=ns.out_dtype)
@@ -151,7 +189,10 @@ def predict(argv=None):
     metas = dict(files)
     for grp in p["groups"]:                                # every refusal before anything runs on the device
         fi, pi = grp[0]
-        check_request(pred.args, *metas[p["order"][fi]][pi], in_max=ns.in_max, out_dtype=ns.out_dtype)
+        try:
+            check_request(pred.args, *metas[p["order"][fi]][pi], in_max=ns.in_max, out_dtype=ns.out_dtype, resolution=ns.resolution)
+        except PredictError as e:
+            raise PredictError(f"{basename(p['order'][fi])}, page {pi}: {e}") if ns.resolution else e
     os.makedirs(out_dir, exist_ok=True)
     DLLogger.init_arb(log_dir=out_dir, is_master=True, reset=True)
     DLLogger.log(f"predict: {len(files)} file(s), {sum(len(g) for g in p['groups'])} page(s) in {len(p['groups'])} group(s) "
@@ -160,6 +201,7 @@ def predict(argv=None):
     n_pages = [len(metas[f]) for f in p["order"]]
     last_group = {fi: gi for gi, grp in enumerate(p["groups"]) for fi, _ in grp}
     cache, results, ms, failed = {}, {}, {}, set()
+    res_pages, report = {}, {}
     for gi, grp in enumerate(p["groups"]):
         for fi in {fi for fi, _ in grp}:
             if fi not in cache:
@@ -167,7 +209,7 @@ def predict(argv=None):
         stack = np.stack([cache[fi][pi] for fi, pi in grp])
         t0 = time.perf_counter()
         try:
-            res = pred.run(stack)
+            res = pred.run(stack, resolution=True) if ns.resolution else pred.run(stack)
         except NonFiniteError:
             res = None
             failed.update(fi for fi, _ in grp)
@@ -176,6 +218,8 @@ def predict(argv=None):
             ms[fi] = ms.get(fi, 0.0) + dt_ms / len(grp)
             if res is not None:
                 results.setdefault(fi, {})[pi] = res[k]
+                if ns.resolution:
+                    res_pages.setdefault(fi, {})[pi] = pred.last_resolution[k]
         for fi in sorted({fi for fi, _ in grp}):
             if last_group[fi] != gi:
                 continue
@@ -186,8 +230,13 @@ def predict(argv=None):
             else:
                 write_pages(p["outputs"][fi], [results[fi][k] for k in range(n_pages[fi])])
                 DLLogger.log(f"{what} -> {basename(p['outputs'][fi])}")
+                if ns.resolution:
+                    report[name] = resolution_rows(res_pages.pop(fi))
+                    DLLogger.log(resolution_line(name, report[name]))
             cache.pop(fi, None)
             results.pop(fi, None)
+    if ns.resolution:
+        write_resolution(out_dir, report)
     if failed:
         DLLogger.log(f"predict: {len(failed)} of {len(files)} file(s) not written")
     return 1 if failed else 0

@@ -2408,6 +2408,28 @@ def metrics_frc_lv(E, Hh, levels=255, threshold=FRC_THRESHOLD, inputs_are_levels
     return curve, cut
 
 
+DECORR_CURVES = 21          # the unfiltered curve and two banks of ten high-pass widths
+
+
+def metrics_decorr_lv(X, levels=255, inputs_are_levels=False, curves=False):
+    """image decorrelation analysis of every image of X at ``levels`` grey levels in float64 (include/srhip.h states it): fp64
+    [B, 5] = cut (the resolution as a fraction of Nyquist, 0: none found), ring, amp, sigma, side of the centred square
+    (``frc_side``); with ``curves`` also the 21 curves, fp64 [B, 21, S/2 + 1], and their peak rings, int32 [B, 21]"""
+    _chk(X)
+    X = X.float().contiguous()
+    B = X.shape[0]
+    H, W = X.shape[-2:]
+    S = frc_side(H, W)
+    n = max(lib.srhip_metrics_decorr_lv_ws(B, H, W), 1)
+    ws = SCRATCH.get("decorr_lv_ws", n, torch.float64, X.device)
+    out = torch.empty(B, 5, dtype=torch.float64, device=X.device)
+    cv = torch.empty(B, DECORR_CURVES, S // 2 + 1, dtype=torch.float64, device=X.device) if curves else None
+    pk = torch.empty(B, DECORR_CURVES, dtype=torch.int32, device=X.device) if curves else None
+    call("srhip_metrics_decorr_lv", _p(X), B, H, W, _levels(levels, "metrics_decorr_lv"), int(inputs_are_levels), _p(ws), ws.numel(),
+         _p(out), _p(cv), _p(pk), _st())
+    return (out, cv, pk) if curves else out
+
+
 # ------------------------------------------------------------------ optimizers
 def adam_step(p, g, m, v, step, lr, b1=0.9, b2=0.999, eps=1e-8, wd=0.0, gscale=1.0, skip_flag=None):
     _chk(p, g, m, v, skip_flag)

@@ -14,7 +14,14 @@ the reference has no such path, so nothing pins the quality of that combination.
 
 What cannot be done is refused by name before anything runs on the device (``PredictError``): 16-bit pages with SRCNN (its
 input is cv2's fixed-point cubic interpolation of a uint8 image) or DSR-Splines (one spline net per grey level 0 .. 255),
-pages too small for the padding rule, an ``in_max`` above the pages' range."""
+pages too small for the padding rule, an ``in_max`` above the pages' range.
+
+``run(pages, resolution=True)`` (predict.py --resolution True) also says what the run produced, with no target to compare with:
+image decorrelation analysis (what ``dlib.metrics.decorr`` returns; include/srhip.h: srhip_metrics_decorr_lv) of every ingested LR page, at
+the levels ``in_max``, and of the net's output for it, at 255 levels for uint8 pages and 65535 otherwise.  That is two more calls
+a group and two small downloads; ``Predictor.last_resolution`` then holds one ``resolution_record`` per page.  The returned pages
+are those of a run without the option, bit for bit.  Refused with the option: a page with a side below 32, an ``in_max`` below
+255."""
 import os
 from os.path import join
 
@@ -25,6 +32,8 @@ from dlib.utils.own_options import in_levels
 
 OUT_DTYPES = ("same", "uint8", "uint16", "float32")
 _RANGE = {"uint8": 255, "uint16": 65535}
+RESOLUTION_MIN_SIDE = 32        # srhip.ops.FRC_MIN_SIDE, without the library
+RESOLUTION_MIN_LEVELS = 255
 
 
 class PredictError(ValueError):
@@ -64,7 +73,19 @@ def padded_size(args, H, W):
     return (H // wsz + 1) * wsz, (W // wsz + 1) * wsz
 
 
-def check_request(args, dtype, H, W, in_max=None, out_dtype="same"):
+def resolution_record(scale, r_in, r_out):
+    """one page of ``Predictor.last_resolution`` from {'side', 'cut', 'amp'} of the LR page and of the output:
+    {'in': {side, cut, res_px, amp}, 'out': {...}, 'gain'}.  res_px = 2 / cut in that image's own pixels (None: cut is 0, no
+    resolution was found); gain = (res_px_in * scale) / res_px_out, both in output pixels (None when either is)."""
+    def one(r):
+        cut = float(r["cut"])
+        return {"side": int(r["side"]), "cut": cut, "res_px": 2.0 / cut if cut > 0 else None, "amp": float(r["amp"])}
+    a, b = one(r_in), one(r_out)
+    both = a["res_px"] is not None and b["res_px"] is not None
+    return {"in": a, "out": b, "gain": (a["res_px"] * scale) / b["res_px"] if both else None}
+
+
+def check_request(args, dtype, H, W, in_max=None, out_dtype="same", resolution=False):
     """Raises PredictError for what this path refuses; returns (in_max, output dtype name).  No device use."""
     name = np.dtype(dtype).name
     if name not in _RANGE:
@@ -91,6 +112,12 @@ def check_request(args, dtype, H, W, in_max=None, out_dtype="same"):
     if Hp - H > H or Wp - W > W:
         raise PredictError(f"a {H} x {W} page is too small: the padding to {Hp} x {Wp} flips a strip of {Hp - H} rows / "
                            f"{Wp - W} columns of the page, more than it has")
+    if resolution and min(H, W) < RESOLUTION_MIN_SIDE:
+        raise PredictError(f"--resolution True: a {H} x {W} page is too small, the decorrelation analysis needs both sides to be "
+                           f"at least {RESOLUTION_MIN_SIDE}")
+    if resolution and in_max < RESOLUTION_MIN_LEVELS:
+        raise PredictError(f"--resolution True: in_max {in_max} is below {RESOLUTION_MIN_LEVELS}, the smallest white level of "
+                           f"the decorrelation analysis")
     return int(in_max), (name if out_dtype == "same" else out_dtype)
 
 
@@ -111,6 +138,7 @@ class Predictor:
         self.test_mode, self.test_refield, self.test_min_size = int(test_mode), int(test_refield), int(test_min_size)
         self.batch, self.in_max, self.out_dtype = int(batch), in_max, out_dtype
         self._model = None
+        self.last_resolution = None      # run(pages, resolution=True): one resolution_record per page
 
     @property
     def model(self):
@@ -129,21 +157,25 @@ class Predictor:
     def out_shape(self, H, W):
         return H * self.scale, W * self.scale
 
-    def run(self, pages):
+    def run(self, pages, resolution=False):
         """pages: np.ndarray [N, H, W], uint8 or uint16 -> np.ndarray [N, scale H, scale W] of the output dtype, the pages in
-        order in groups of at most ``batch``.  A group whose output is not finite raises NonFiniteError."""
+        order in groups of at most ``batch``.  A group whose output is not finite raises NonFiniteError.  ``resolution``: the
+        same pages, and ``last_resolution`` holds a ``resolution_record`` for every one of them (module docstring)."""
         pages = np.asarray(pages)
         if pages.ndim != 3:
             raise PredictError(f"pages [N, H, W] (got shape {pages.shape})")
         N, H, W = pages.shape
-        in_max, out_name = check_request(self.args, pages.dtype, H, W, self.in_max, self.out_dtype)
+        in_max, out_name = check_request(self.args, pages.dtype, H, W, self.in_max, self.out_dtype, resolution)
         sH, sW = self.out_shape(H, W)
         out = np.empty((N, sH, sW), dtype=out_name)
+        self.last_resolution = None
+        records = [] if resolution else None
         for g0 in range(0, N, self.batch):
-            out[g0:g0 + self.batch] = self._run_group(pages[g0:g0 + self.batch], g0, in_max, out_name)
+            out[g0:g0 + self.batch] = self._run_group(pages[g0:g0 + self.batch], g0, in_max, out_name, records)
+        self.last_resolution = records
         return out
 
-    def _run_group(self, grp, first, in_max, out_name):
+    def _run_group(self, grp, first, in_max, out_name, records=None):
         import torch
         from srhip import ops
         model = self.model
@@ -155,6 +187,8 @@ class Predictor:
         if self.args.netG["net_type"] == constants.SRCNN:
             from dlib.datasets import lowres
             data["l_to_h_img"] = ops.u8_to_unit(lowres.l_to_h(src, (sH, sW))).view(B, 1, sH, sW)
+        if records is not None:                                     # the LR pages as ingested, without the padding
+            r_in = ops.metrics_decorr_lv(data["l_im"][:, :, :H, :W].contiguous(), in_max)
         model.feed_data(data, need_H=False)
         if self.test_mode == 0:
             model.test()
@@ -163,6 +197,8 @@ class Predictor:
         E = model.E.detach().float().contiguous()
         if tuple(E.shape) != (B, 1, Hp * self.scale, Wp * self.scale):
             raise RuntimeError(f"the net returned {tuple(E.shape)} for an input of {(B, 1, Hp, Wp)} at scale {self.scale}")
+        if records is not None:                                     # the output before it is rounded to the file's levels
+            r_out = ops.metrics_decorr_lv(E[:, :, :sH, :sW].contiguous(), 255 if out_name == "uint8" else 65535)
         if out_name == "float32":
             res = E[:, 0, :sH, :sW].cpu().numpy()
             bad = not np.isfinite(res).all()
@@ -177,4 +213,7 @@ class Predictor:
             res, bad = host[16:].view(out_name).reshape(B, sH, sW), bool(host[:4].view(np.int32)[0])
         if bad:
             raise NonFiniteError(range(first, first + B))
+        if records is not None:
+            rows = zip(r_in.cpu().tolist(), r_out.cpu().tolist())       # [B][5] = cut, ring, amp, sigma, side: two downloads
+            records.extend(resolution_record(self.scale, *({"cut": r[0], "amp": r[2], "side": r[4]} for r in pair)) for pair in rows)
         return res
