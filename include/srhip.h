@@ -1051,6 +1051,51 @@ int srhip_metrics_frc_lv(const float* E, const float* Hh, int B, int H, int W, i
 long srhip_metrics_decorr_lv_ws(int B, int H, int W);
 int srhip_metrics_decorr_lv(const float* img, int B, int H, int W, int L, int inputs_are_levels, double* workspace,
                             long workspace_doubles, double* out, double* curves, int* peaks, void* stream);
+/* Resolution-scaled error (predict.py --consistency; Culley et al., "Quantitative mapping and minimization of super-resolution
+ * optical imaging artifacts", Nature Methods 15 (2018), NanoJ-SQUIRREL): is a super-resolved image still an image of what was
+ * acquired?  The output is degraded back to the acquisition -- blurred, binned, rescaled linearly in intensity --, the blur that
+ * explains the LR page best is chosen, and how well it explains it is reported, with a map of where it does not.  No target is
+ * needed.  This text is the definition.
+ * Inputs, per page: E, the net's float32 output cropped to [s h][s w], as returned (not clamped, not quantised); L, the ingested
+ * LR page, float32 [h][w] (what srhip_ingest_pad made of the file, without the padding); s, the integer scale, 2 .. 8.
+ * Candidate blurs: sigma = q s / 64 HR pixels, q an integer 0 .. 127.  The largest is 15.875 at s = 8, radius
+ * int(4 sigma + 0.5) = 64, srhip_psf_bin's limit: that is why s stops at 8.  The weights of candidate q are
+ * psf_bin_weights(q s / 64, s) of dlib/datasets/lowres.py (box_s (*) scipy's normalised Gaussian, 2 r + s of them); all 128 are
+ * built once per scale on the host and passed as one table, weights_table [128][136] float64, row q holding its 2 r + s weights
+ * and zeros behind them.  The kernels compute no exponential.
+ * Model image: b_q[i][j] = sum_t w_q[t] R_q[reflect(i s - r + t)][j],  R_q[y][j] = sum_t w_q[t] E[y][reflect(j s - r + t)], taps
+ * in ascending order, every product and every sum rounded on its own in float64, NO rounding to float32 in between (the one
+ * difference from srhip_psf_bin, whose tmp is float32); the border is scipy's 'reflect' at any distance: the radius may exceed
+ * the image.
+ * Sums over all n = h w pixels in float64: Sb, Sbb, Sbl, Sl, Sll of b, b^2, b l, l, l^2.  C_bb = Sbb - Sb Sb / n, C_ll and C_bl
+ * likewise.
+ * Score: score(q) = C_bl |C_bl| / (C_bb C_ll), the signed r^2, so that an anticorrelated model never wins; 0 when C_bb <= 0 or
+ * C_ll <= 0.
+ * Search: two banks of 16.  Coarse: q = 8 k, k = 0 .. 15.  Fine: q = max(0, q_coarse + m - 8), m = 0 .. 15, around the coarse
+ * winner.  A winner is the FIRST index of the largest score.  The computation of a candidate does not depend on its slot:
+ * duplicate q = 0 entries of the fine bank give identical bits.  The result is the fine bank's winner.
+ * Result out[b][8], float64: sigma (HR pixels), alpha = C_bl / C_bb, beta = (Sl - alpha Sb) / n, rsp = sign(score) sqrt(|score|),
+ * rse = sqrt(max(0, C_ll - C_bl^2 / C_bb) / n) in units of the white level, q, n, and one reserved 0.  A degenerate page (the
+ * winner has C_bb <= 0 or C_ll <= 0: a constant L, or a constant b for every candidate) reports sigma = 0, alpha = 0,
+ * beta = Sl / n, rsp = 0, rse = sqrt(max(0, C_ll) / n), q = 0.
+ * Optional outputs (NULL: not written): scores [B][32] float64 and qs [B][32] int, the coarse bank and then the fine bank;
+ * residual [B][h][w] float32 = float32(double(L) - (alpha b_q* + beta)) of the winner, SIGNED: positive where the acquisition is
+ * brighter than the output explains.
+ * How this departs from the authors' code: a fixed two-bank grid instead of particle-swarm optimisation; a Gaussian
+ * resolution-scaling function only; no sub-pixel registration (the nets here place LR pixel (i, j) on HR pixels [s i, s i + s));
+ * a signed map; 'reflect' borders.  A figure from this code is comparable with another figure from this code.
+ * Strides are in elements: E_plane / E_ld between pages / rows of E, L_plane / L_ld of L, so a cropped view of a padded tensor
+ * goes in without a copy.  The candidate images never exist in memory: a block owns (page, candidate, 64 / s LR rows) and keeps
+ * the row correlations it needs in LDS; per block five sums leave the CU, they are added in a fixed order, nothing is
+ * accumulated with atomics.  Two calls give the same bits, and a page's result does not depend on B or on its place in the batch.
+ * Five launches (four without the map), no host synchronisation, no allocation.
+ * Refused (-22): a NULL E, L, weights_table, workspace or out; s outside 2 .. 8; h or w below 4; B outside 1 .. 65535; a row
+ * stride below the row (or, for B > 1, a plane stride below the page); a workspace below srhip_consistency_ws's figure
+ * (*doubles; 8-byte aligned); workspace, out, scores, qs or residual overlapping each other or an input. */
+int srhip_consistency_ws(int B, int h, int w, int s, long* doubles);
+int srhip_consistency(const float* E, long E_plane, long E_ld, const float* L, long L_plane, long L_ld, int B, int h, int w, int s,
+                      const double* weights_table, double* workspace, long workspace_doubles, double* out, double* scores, int* qs,
+                      float* residual, void* stream);
 
 /* Weight (and bias) gradients of up to 40 3x3 convolutions of ONE shape -- the body of an
  * EDSR-style stack (network_nlsn.py:72-93,325-345 backward) -- in one contraction launch plus one

@@ -27,6 +27,10 @@ centred power-of-two square, float64; both sides at least 32.
 ``decorr`` (not a reference function; ``predict.py --resolution``): image decorrelation analysis (Descloux, Grussmayer, Radenovic
 2019), the resolution of ONE image with no target and no second acquisition; include/srhip.h (srhip_metrics_decorr_lv) states it.
 The square, the window and the rings are the FRC's; a call of its own, never part of ``sweep``.
+
+``consistency`` (not a reference function; ``predict.py --consistency``): the resolution-scaled error of NanoJ-SQUIRREL (Culley et
+al. 2018), how well a super-resolved image, blurred, binned and rescaled, explains the LR page it was made from -- RSP, RSE and
+the signed error map, with no target; include/srhip.h (srhip_consistency) states it.  A call of its own, never part of ``sweep``.
 """
 import torch
 
@@ -34,7 +38,7 @@ from srhip import ops
 
 __all__ = ['tensor2uint82float', 'tensor2levels', 'mbatch_gpu_calculate_psnr', 'mbatch_gpu_calculate_mse',
            'mbatch_gpu_calculate_nrmse', 'mbatch_gpu_calculate_ssim', 'mbatch_gpu_calculate_msssim', 'sweep',
-           'frc', 'mbatch_gpu_calculate_frc', 'decorr']
+           'frc', 'mbatch_gpu_calculate_frc', 'decorr', 'consistency']
 
 
 def _need_cuda(t):
@@ -160,4 +164,26 @@ def decorr(X, levels=255, inputs_are_levels=False, curves=False):
          "sigma": out[:, 3].contiguous(), "side": ops.frc_side(*X.shape[-2:])}
     if curves:
         d["curves"], d["peaks"] = res[1], res[2]
+    return d
+
+
+def consistency(E, L, scale, scores=False, residual=False):
+    """(not a reference function) resolution-scaled error of the outputs E, (B,1,scale h,scale w), against the LR pages L,
+    (B,1,h,w), both float32 in units of the white level, strided views welcome; scale 2 .. 8.  Returns {'sigma': (B,) float64, the
+    blur in HR pixels under which E explains L best, 'alpha', 'beta': (B,) float64, the linear intensity rescaling, 'rsp': (B,)
+    float64, the Pearson coefficient of the degraded E with L, 'rse': (B,) float64, the RMS residual in units of the white level,
+    'q': (B,) int64, sigma = q scale / 64}; with ``scores`` also 'scores': (B, 32) float64 and 'qs': (B, 32) int32, the signed r^2
+    of the coarse and the fine bank and their q; with ``residual`` also 'residual': (B, h, w) float32, L minus the rescaled
+    degraded E, positive where the acquisition is brighter than the output explains."""
+    _need_cuda(E)
+    _need_cuda(L)
+    res = ops.consistency(E, L, scale, scores, residual)
+    res = res if isinstance(res, tuple) else (res,)
+    out = res[0]
+    d = {"sigma": out[:, 0].contiguous(), "alpha": out[:, 1].contiguous(), "beta": out[:, 2].contiguous(),
+         "rsp": out[:, 3].contiguous(), "rse": out[:, 4].contiguous(), "q": out[:, 5].to(torch.int64)}
+    if scores:
+        d["scores"], d["qs"] = res[1], res[2]
+    if residual:
+        d["residual"] = res[-1]
     return d

@@ -4,6 +4,7 @@
     python predict.py --exp_path <folder> --input <file | directory> [--output <directory>]
                       [--cudaid 0] [--batch 8] [--in_max N] [--out_dtype same|uint8|uint16|float32]
                       [--test_mode {0..4} [--test_refield 32] [--test_min_size 256]] [--resolution True]
+                      [--consistency True [--consistency_maps True]]
 
 <folder> is the experiment directory ``eval.py`` reads (``config_model.yml``, ``best-models/G-model.pth``).  Inputs are
 single-channel ``.tif`` / ``.tiff`` / ``.png`` files of PIL mode ``L`` or ``I;16`` (a grey palette counts as ``L``); every
@@ -21,7 +22,17 @@ include/srhip.h: srhip_metrics_decorr_lv), a resolution figure from one image wi
 output.  ``<output>/resolution.yml`` then holds ``{file: [{page, in: {side, cut, res_px, amp}, out: {...}, gain}]}``: ``cut`` a
 fraction of Nyquist, ``res_px = 2 / cut`` in that image's own pixels (null: none found), ``gain = res_px_in * scale /
 res_px_out``; one more log line per file carries the means.  The output files are those of a run without the option.  Every
-page needs both sides to be at least 32."""
+page needs both sides to be at least 32.
+
+``--consistency True`` (default off) checks every output against the LR page it was made from: the resolution-scaled error of
+NanoJ-SQUIRREL (Culley et al. 2018; include/srhip.h: srhip_consistency).  The float output is blurred, binned by the scale and
+rescaled linearly so that it explains the LR page best; ``<output>/consistency.yml`` then holds ``{file: [{page, sigma_px,
+sigma_lr, alpha, beta, rsp, rse, rse_levels}]}``: the blur in output and in LR pixels, the intensity rescaling, the Pearson
+coefficient RSP, the RMS residual RSE in units of the white level and in the file's grey levels; one more log line per file
+carries the mean RSP and RSE.  ``--consistency_maps True`` (only with ``--consistency True``) also writes
+``<stem>_x<scale>_residual.tif``: float32 (TIFF mode ``F``), one page per input page at the LR size, LR page minus rescaled
+degraded output, positive where the acquisition is brighter than the output explains.  Scales 2 .. 8, both sides of a page at
+least 4.  A file that was not written gets no record and no map."""
 import argparse
 import os
 import sys
@@ -163,6 +174,34 @@ def write_resolution(out_dir, report):
         yaml.safe_dump(report, f, sort_keys=False)
 
 
+def consistency_rows(records):
+    """{page index: consistency_record} of one file -> its list in consistency.yml, [{page, sigma_px, ...}] in page order"""
+    return [{"page": k, **records[k]} for k in sorted(records)]
+
+
+def consistency_means(rows):
+    """(mean RSP, mean RSE, mean RSE in grey levels) over the pages of a file"""
+    return tuple(sum(r[k] for r in rows) / len(rows) for k in ("rsp", "rse", "rse_levels"))
+
+
+def consistency_line(name, rows):
+    """the log line of one file under --consistency True"""
+    rsp, rse, lv = consistency_means(rows)
+    return (f"{name}: consistency RSP {rsp:.4f}, RSE {rse:.5f} of the white level = {lv:.2f} grey level(s) "
+            f"[MEAN over {len(rows)} page(s), against the LR page]")
+
+
+def write_consistency(out_dir, report):
+    import yaml
+    with open(join(out_dir, "consistency.yml"), "w") as f:
+        yaml.safe_dump(report, f, sort_keys=False)
+
+
+def residual_path(output):
+    """<stem>_x<scale><ext> -> <stem>_x<scale>_residual.tif beside it"""
+    return splitext(output)[0] + "_residual.tif"
+
+
 def predict(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--exp_path", type=str, required=True)
@@ -178,7 +217,13 @@ def predict(argv=None):
     ap.add_argument("--test_min_size", type=int, default=256)
     ap.add_argument("--resolution", type=str2bool, default=False,
                     help="also write resolution.yml: the decorrelation-analysis resolution of every LR page and of its output")
+    ap.add_argument("--consistency", type=str2bool, default=False,
+                    help="also write consistency.yml: the resolution-scaled error (RSP, RSE) of every output against its LR page")
+    ap.add_argument("--consistency_maps", type=str2bool, default=False,
+                    help="with --consistency True: also write <stem>_x<scale>_residual.tif, the signed float32 error maps")
     ns = ap.parse_args(argv)
+    if ns.consistency_maps and not ns.consistency:
+        raise PredictError("--consistency_maps True needs --consistency True: the maps belong to the resolution-scaled error")
     pred = Predictor(ns.exp_path, cudaid=ns.cudaid, test_mode=ns.test_mode, test_refield=ns.test_refield,
                      test_min_size=ns.test_min_size, batch=ns.batch, in_max=ns.in_max, out_dtype=ns.out_dtype)
     out_dir = ns.output or join(ns.exp_path, "predict", basename(normpath(ns.input)))
@@ -190,9 +235,10 @@ def predict(argv=None):
     for grp in p["groups"]:                                # every refusal before anything runs on the device
         fi, pi = grp[0]
         try:
-            check_request(pred.args, *metas[p["order"][fi]][pi], in_max=ns.in_max, out_dtype=ns.out_dtype, resolution=ns.resolution)
+            check_request(pred.args, *metas[p["order"][fi]][pi], in_max=ns.in_max, out_dtype=ns.out_dtype, resolution=ns.resolution,
+                          consistency=ns.consistency)
         except PredictError as e:
-            raise PredictError(f"{basename(p['order'][fi])}, page {pi}: {e}") if ns.resolution else e
+            raise PredictError(f"{basename(p['order'][fi])}, page {pi}: {e}") if ns.resolution or ns.consistency else e
     os.makedirs(out_dir, exist_ok=True)
     DLLogger.init_arb(log_dir=out_dir, is_master=True, reset=True)
     DLLogger.log(f"predict: {len(files)} file(s), {sum(len(g) for g in p['groups'])} page(s) in {len(p['groups'])} group(s) "
@@ -202,6 +248,8 @@ def predict(argv=None):
     last_group = {fi: gi for gi, grp in enumerate(p["groups"]) for fi, _ in grp}
     cache, results, ms, failed = {}, {}, {}, set()
     res_pages, report = {}, {}
+    con_pages, con_maps, con_report = {}, {}, {}
+    extra = {k: True for k in ("resolution", "consistency", "consistency_maps") if getattr(ns, k)}
     for gi, grp in enumerate(p["groups"]):
         for fi in {fi for fi, _ in grp}:
             if fi not in cache:
@@ -209,7 +257,7 @@ def predict(argv=None):
         stack = np.stack([cache[fi][pi] for fi, pi in grp])
         t0 = time.perf_counter()
         try:
-            res = pred.run(stack, resolution=True) if ns.resolution else pred.run(stack)
+            res = pred.run(stack, **extra)
         except NonFiniteError:
             res = None
             failed.update(fi for fi, _ in grp)
@@ -220,6 +268,10 @@ def predict(argv=None):
                 results.setdefault(fi, {})[pi] = res[k]
                 if ns.resolution:
                     res_pages.setdefault(fi, {})[pi] = pred.last_resolution[k]
+                if ns.consistency:
+                    con_pages.setdefault(fi, {})[pi] = pred.last_consistency[k]
+                if ns.consistency_maps:
+                    con_maps.setdefault(fi, {})[pi] = pred.last_residuals[k]
         for fi in sorted({fi for fi, _ in grp}):
             if last_group[fi] != gi:
                 continue
@@ -233,10 +285,19 @@ def predict(argv=None):
                 if ns.resolution:
                     report[name] = resolution_rows(res_pages.pop(fi))
                     DLLogger.log(resolution_line(name, report[name]))
+                if ns.consistency:
+                    con_report[name] = consistency_rows(con_pages[fi])
+                    DLLogger.log(consistency_line(name, con_report[name]))
+                if ns.consistency_maps:
+                    write_pages(residual_path(p["outputs"][fi]), [con_maps[fi][k] for k in range(n_pages[fi])])
             cache.pop(fi, None)
             results.pop(fi, None)
+            con_pages.pop(fi, None)
+            con_maps.pop(fi, None)
     if ns.resolution:
         write_resolution(out_dir, report)
+    if ns.consistency:
+        write_consistency(out_dir, con_report)
     if failed:
         DLLogger.log(f"predict: {len(failed)} of {len(files)} file(s) not written")
     return 1 if failed else 0

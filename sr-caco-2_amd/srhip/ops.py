@@ -2430,6 +2430,82 @@ def metrics_decorr_lv(X, levels=255, inputs_are_levels=False, curves=False):
     return (out, cv, pk) if curves else out
 
 
+CONSISTENCY_Q = 128                 # candidate blurs of srhip_consistency: sigma = q s / 64 HR pixels, q = 0 .. 127
+CONSISTENCY_PITCH = 2 * LR_BLUR_MAX_RADIUS + 8      # doubles a row of its weight table
+CONSISTENCY_MIN_SCALE, CONSISTENCY_MAX_SCALE, CONSISTENCY_MIN_SIDE = 2, 8, 4
+_CONSISTENCY_TABLES = {}
+
+
+def _consistency_scale(s, who):
+    if isinstance(s, bool) or not isinstance(s, int) or not CONSISTENCY_MIN_SCALE <= s <= CONSISTENCY_MAX_SCALE:
+        raise SrhipError(f"{who}: the scale s is an integer {CONSISTENCY_MIN_SCALE} .. {CONSISTENCY_MAX_SCALE} (got {s!r})")
+    return s
+
+
+def consistency_table(s):
+    """numpy float64 [128, 136], no device use: row q holds dlib.datasets.lowres.psf_bin_weights(q s / 64, s), its 2 r + s weights
+    with zeros behind them (the weight table of srhip_consistency; include/srhip.h)"""
+    import numpy as np
+    from dlib.datasets import lowres
+    s = _consistency_scale(s, "consistency_table")
+    tab = np.zeros((CONSISTENCY_Q, CONSISTENCY_PITCH), dtype=np.float64)
+    for q in range(CONSISTENCY_Q):
+        w = lowres.psf_bin_weights(q * s / 64.0, s)
+        tab[q, :w.size] = w
+    return tab
+
+
+def consistency_weights(s, device="cuda"):
+    """consistency_table(s) on the device: built once per scale and device, then cached"""
+    key = (_consistency_scale(s, "consistency_weights"), str(torch.device(device)))
+    if key not in _CONSISTENCY_TABLES:
+        _CONSISTENCY_TABLES[key] = torch.from_numpy(consistency_table(s)).to(device)
+    return _CONSISTENCY_TABLES[key]
+
+
+def _consistency_view(t, name):
+    """(plane stride, row stride, rows, columns) of a float32 CUDA batch [B, 1, H, W] or [B, H, W] whose rows are contiguous:
+    any other stride is taken as it is, so a cropped view of a padded tensor needs no copy"""
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise SrhipError("srhip ops need CUDA/HIP tensors (no CPU fallback exists)")
+    if t.dim() == 4 and t.shape[1] == 1:
+        t = t[:, 0]
+    if not (t.dim() == 3 and t.dtype == torch.float32 and t.numel() > 0 and t.stride(2) == 1 and t.stride(1) >= t.shape[2]
+            and (t.shape[0] == 1 or t.stride(0) >= (t.shape[1] - 1) * t.stride(1) + t.shape[2])):
+        raise SrhipError(f"consistency: {name} is a float32 batch [B, 1, H, W] or [B, H, W] with contiguous rows "
+                         f"(got {tuple(t.shape)}, {t.dtype}, strides {tuple(t.stride())})")
+    return t
+
+
+def consistency(E, L, s, scores=False, residual=False):
+    """resolution-scaled error of the outputs E [B, 1, s h, s w] against the LR pages L [B, 1, h, w] (srhip_consistency,
+    consistency.hip; include/srhip.h states the measure, tests/consistency_ref.py restates it in numpy): fp64 [B, 8] = sigma (HR
+    pixels), alpha, beta, rsp, rse, q, n, 0; with ``scores`` also the 32 scores of the two banks, fp64 [B, 32], and their q, int32
+    [B, 32]; with ``residual`` also the signed map float32 [B, h, w].  Returns out, or (out[, scores, qs][, residual]).  Strided
+    views go in as they are."""
+    s = _consistency_scale(s, "consistency")
+    E, L = _consistency_view(E, "E"), _consistency_view(L, "L")
+    B, h, w = L.shape
+    if E.device != L.device or tuple(E.shape) != (B, s * h, s * w):
+        raise SrhipError(f"consistency: E is [{B}, {s * h}, {s * w}] on the device of L, {s} times L's {h} x {w} "
+                         f"(got {tuple(E.shape)})")
+    if min(h, w) < CONSISTENCY_MIN_SIDE:
+        raise SrhipError(f"consistency: both sides of an LR page are at least {CONSISTENCY_MIN_SIDE} (got {h} x {w})")
+    table = consistency_weights(s, L.device)
+    need = ctypes.c_long(0)
+    call("srhip_consistency_ws", B, h, w, s, ctypes.addressof(need))
+    ws = SCRATCH.get("consistency_ws", need.value, torch.float64, L.device)
+    out = torch.empty(B, 8, dtype=torch.float64, device=L.device)
+    sc = torch.empty(B, 32, dtype=torch.float64, device=L.device) if scores else None
+    qs = torch.empty(B, 32, dtype=torch.int32, device=L.device) if scores else None
+    res = torch.empty(B, h, w, dtype=torch.float32, device=L.device) if residual else None
+    call("srhip_consistency", _p(E), E.stride(0), E.stride(1), _p(L), L.stride(0), L.stride(1), B, h, w, s, _p(table), _p(ws),
+         ws.numel(), _p(out), _p(sc), _p(qs), _p(res), _st())
+    if not (scores or residual):
+        return out
+    return (out,) + ((sc, qs) if scores else ()) + ((res,) if residual else ())
+
+
 # ------------------------------------------------------------------ optimizers
 def adam_step(p, g, m, v, step, lr, b1=0.9, b2=0.999, eps=1e-8, wd=0.0, gscale=1.0, skip_flag=None):
     _chk(p, g, m, v, skip_flag)

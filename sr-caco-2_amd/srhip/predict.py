@@ -21,7 +21,16 @@ image decorrelation analysis (what ``dlib.metrics.decorr`` returns; include/srhi
 the levels ``in_max``, and of the net's output for it, at 255 levels for uint8 pages and 65535 otherwise.  That is two more calls
 a group and two small downloads; ``Predictor.last_resolution`` then holds one ``resolution_record`` per page.  The returned pages
 are those of a run without the option, bit for bit.  Refused with the option: a page with a side below 32, an ``in_max`` below
-255."""
+255.
+
+``run(pages, consistency=True)`` (predict.py --consistency True) asks the other question of an output without ground truth: is
+it still an image of what was acquired?  The resolution-scaled error of NanoJ-SQUIRREL (Culley et al. 2018; what
+``dlib.metrics.consistency`` returns; include/srhip.h: srhip_consistency): the float output, blurred, binned by the scale and
+rescaled linearly, against the ingested LR page -- one call a group on strided views of the two tensors the run holds anyway,
+and one small download.  ``Predictor.last_consistency`` then holds one ``consistency_record`` per page; with
+``consistency_maps=True`` ``Predictor.last_residuals`` holds the signed float32 error maps [N, H, W].  The returned pages are
+those of a run without the option, bit for bit, and it combines with ``resolution=True``.  Refused with the option: a scale
+outside 2 .. 8, a page with a side below 4."""
 import os
 from os.path import join
 
@@ -34,6 +43,8 @@ OUT_DTYPES = ("same", "uint8", "uint16", "float32")
 _RANGE = {"uint8": 255, "uint16": 65535}
 RESOLUTION_MIN_SIDE = 32        # srhip.ops.FRC_MIN_SIDE, without the library
 RESOLUTION_MIN_LEVELS = 255
+CONSISTENCY_SCALES = (2, 8)     # srhip.ops.CONSISTENCY_MIN_SCALE / _MAX_SCALE / _MIN_SIDE, without the library
+CONSISTENCY_MIN_SIDE = 4
 
 
 class PredictError(ValueError):
@@ -85,7 +96,16 @@ def resolution_record(scale, r_in, r_out):
     return {"in": a, "out": b, "gain": (a["res_px"] * scale) / b["res_px"] if both else None}
 
 
-def check_request(args, dtype, H, W, in_max=None, out_dtype="same", resolution=False):
+def consistency_record(scale, in_max, row):
+    """one page of ``Predictor.last_consistency`` from its row of srhip_consistency's result (sigma, alpha, beta, rsp, rse, ...):
+    {sigma_px, sigma_lr, alpha, beta, rsp, rse, rse_levels}.  sigma_px is the blur in output pixels, sigma_lr = sigma_px / scale
+    the same in LR pixels; rse is in units of the white level, rse_levels = rse * in_max in the grey levels of the input file."""
+    sigma, alpha, beta, rsp, rse = (float(v) for v in row[:5])
+    return {"sigma_px": sigma, "sigma_lr": sigma / scale, "alpha": alpha, "beta": beta, "rsp": rsp, "rse": rse,
+            "rse_levels": rse * in_max}
+
+
+def check_request(args, dtype, H, W, in_max=None, out_dtype="same", resolution=False, consistency=False):
     """Raises PredictError for what this path refuses; returns (in_max, output dtype name).  No device use."""
     name = np.dtype(dtype).name
     if name not in _RANGE:
@@ -118,6 +138,13 @@ def check_request(args, dtype, H, W, in_max=None, out_dtype="same", resolution=F
     if resolution and in_max < RESOLUTION_MIN_LEVELS:
         raise PredictError(f"--resolution True: in_max {in_max} is below {RESOLUTION_MIN_LEVELS}, the smallest white level of "
                            f"the decorrelation analysis")
+    if consistency and not CONSISTENCY_SCALES[0] <= int(args.scale) <= CONSISTENCY_SCALES[1]:
+        raise PredictError(f"--consistency True: scale {int(args.scale)} is outside {CONSISTENCY_SCALES[0]} .. "
+                           f"{CONSISTENCY_SCALES[1]}, the scales of the resolution-scaled error (its largest blur has the "
+                           f"radius 64 at scale 8)")
+    if consistency and min(H, W) < CONSISTENCY_MIN_SIDE:
+        raise PredictError(f"--consistency True: a {H} x {W} page is too small, the resolution-scaled error needs both sides to "
+                           f"be at least {CONSISTENCY_MIN_SIDE}")
     return int(in_max), (name if out_dtype == "same" else out_dtype)
 
 
@@ -139,6 +166,8 @@ class Predictor:
         self.batch, self.in_max, self.out_dtype = int(batch), in_max, out_dtype
         self._model = None
         self.last_resolution = None      # run(pages, resolution=True): one resolution_record per page
+        self.last_consistency = None     # run(pages, consistency=True): one consistency_record per page
+        self.last_residuals = None       # ... consistency_maps=True: float32 [N, H, W], the signed error maps
 
     @property
     def model(self):
@@ -157,25 +186,34 @@ class Predictor:
     def out_shape(self, H, W):
         return H * self.scale, W * self.scale
 
-    def run(self, pages, resolution=False):
+    def run(self, pages, resolution=False, consistency=False, consistency_maps=False):
         """pages: np.ndarray [N, H, W], uint8 or uint16 -> np.ndarray [N, scale H, scale W] of the output dtype, the pages in
         order in groups of at most ``batch``.  A group whose output is not finite raises NonFiniteError.  ``resolution``: the
-        same pages, and ``last_resolution`` holds a ``resolution_record`` for every one of them (module docstring)."""
+        same pages, and ``last_resolution`` holds a ``resolution_record`` for every one of them; ``consistency``: the same
+        pages, and ``last_consistency`` holds a ``consistency_record`` for every one of them, ``last_residuals`` their error
+        maps under ``consistency_maps`` (module docstring)."""
         pages = np.asarray(pages)
         if pages.ndim != 3:
             raise PredictError(f"pages [N, H, W] (got shape {pages.shape})")
         N, H, W = pages.shape
-        in_max, out_name = check_request(self.args, pages.dtype, H, W, self.in_max, self.out_dtype, resolution)
+        if consistency_maps and not consistency:
+            raise PredictError("consistency_maps=True needs consistency=True: the maps belong to the resolution-scaled error")
+        in_max, out_name = check_request(self.args, pages.dtype, H, W, self.in_max, self.out_dtype, resolution, consistency)
         sH, sW = self.out_shape(H, W)
         out = np.empty((N, sH, sW), dtype=out_name)
-        self.last_resolution = None
+        self.last_resolution = self.last_consistency = self.last_residuals = None
         records = [] if resolution else None
+        cons = {"records": [], "maps": [] if consistency_maps else None} if consistency else None
         for g0 in range(0, N, self.batch):
-            out[g0:g0 + self.batch] = self._run_group(pages[g0:g0 + self.batch], g0, in_max, out_name, records)
+            out[g0:g0 + self.batch] = self._run_group(pages[g0:g0 + self.batch], g0, in_max, out_name, records, cons)
         self.last_resolution = records
+        if consistency:
+            self.last_consistency = cons["records"]
+            if consistency_maps:
+                self.last_residuals = np.concatenate(cons["maps"]) if cons["maps"] else np.empty((0, H, W), np.float32)
         return out
 
-    def _run_group(self, grp, first, in_max, out_name, records=None):
+    def _run_group(self, grp, first, in_max, out_name, records=None, cons=None):
         import torch
         from srhip import ops
         model = self.model
@@ -199,6 +237,8 @@ class Predictor:
             raise RuntimeError(f"the net returned {tuple(E.shape)} for an input of {(B, 1, Hp, Wp)} at scale {self.scale}")
         if records is not None:                                     # the output before it is rounded to the file's levels
             r_out = ops.metrics_decorr_lv(E[:, :, :sH, :sW].contiguous(), 255 if out_name == "uint8" else 65535)
+        if cons is not None:        # the float output as returned against the ingested pages: two strided views, no copy
+            c_out = ops.consistency(E[:, :, :sH, :sW], data["l_im"][:, :, :H, :W], self.scale, residual=cons["maps"] is not None)
         if out_name == "float32":
             res = E[:, 0, :sH, :sW].cpu().numpy()
             bad = not np.isfinite(res).all()
@@ -216,4 +256,9 @@ class Predictor:
         if records is not None:
             rows = zip(r_in.cpu().tolist(), r_out.cpu().tolist())       # [B][5] = cut, ring, amp, sigma, side: two downloads
             records.extend(resolution_record(self.scale, *({"cut": r[0], "amp": r[2], "side": r[4]} for r in pair)) for pair in rows)
+        if cons is not None:
+            rows = (c_out[0] if cons["maps"] is not None else c_out).cpu().tolist()         # [B][8]: one small download
+            cons["records"].extend(consistency_record(self.scale, in_max, r) for r in rows)
+            if cons["maps"] is not None:
+                cons["maps"].append(c_out[1].cpu().numpy())
         return res
